@@ -12,6 +12,12 @@ because its recurrence is sequential).  Inputs: synthetic 48 kHz P-channel
 PCM (tools/aero_synth.cpp), materialised in HBM before the timed region.
 Multi-GPU: one process per GPU, channels sharded (weak scaling), no
 data-path collective; barrier + max-over-ranks timing only.
+
+A plain run (--gpus, --steps, --warmup) sets up, warms up, times the steps
+and prints the result line.  --full adds the measurements that take runs of
+their own: the CPU baseline (the oracle on the host cores) and the second,
+H2D-inclusive timed region.  --dump-outputs DIR writes what the timed steps
+handed back (ItemTap) as DIR/<name>.npy.
 """
 import argparse
 import concurrent.futures as cf
@@ -114,25 +120,32 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--mode', default='oqpsk10500', choices=sorted(MODES) + ['c1', 'c5', 'c5bin'],
                     help='channel kind (default: the BASELINE.json headline, C2 10500-bps OQPSK)')
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20,
+                    help='timed steps (the input block of every timed step is in HBM before the clock starts: '
+                         '0.5 GB per step at 65536 channels)')
     ap.add_argument('--warmup', type=int, default=5,
                     help='untimed steps after the fixed %d-hop lock-in pre-roll' % PREROLL_HOPS)
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the CPU baseline (cpu_baseline, vs_cpu) '
+                         'and, in the continuous modes, the H2D-inclusive second timed region (h2d)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what they handed back as DIR/<name>.npy (see ItemTap)')
     ap.add_argument('--channels', type=int, default=65536, help='VFO channels per GPU (one lane each: 65536 fill the 1024 SIMDs at one wave each)')
     ap.add_argument('--pool', type=int, default=64, help='distinct synthetic streams per GPU')
     ap.add_argument('--cpu-seconds', type=float, default=None,
-                    help='signal seconds per CPU-baseline process (default per mode: ~5-10 s CPU each)')
+                    help='--full: signal seconds per CPU-baseline process (default per mode: ~5-10 s CPU each)')
     ap.add_argument('--cpu-procs', type=int, default=None,
                     help='CPU-baseline processes (default: the host cores this process may use, at most 16 = '
                          'the GPU box CPU share)')
     ap.add_argument('--cpu-runs', type=int, default=3, help='CPU-baseline repetitions (the median is reported)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without its CPU baseline')
     ap.add_argument('--no-dcd-tick', action='store_true',
                     help="continuous OQPSK without AeroL's 1 s DCD timer (AERO_F_DCD_TICK, on by default as in "
                          'bin/aero-decode, whose reference runs the Qt event loop)')
     ap.add_argument('--hw-queues', type=int, default=None,
                     help='GPU_MAX_HW_QUEUES for this run (default: at least 8; applied before HIP initialises)')
     ap.add_argument('--h2d-steps', type=int, default=None,
-                    help='continuous modes: steps of the second, H2D-inclusive timed region (int16 blocks pushed '
+                    help='--full, continuous modes: steps of the second, H2D-inclusive timed region (int16 blocks pushed '
                          'from pinned host memory inside it; default: as many as --steps, so both regions carry '
                          'the same pipeline fill and drain); 0 skips it')
     ap.add_argument('--dist', action='store_true',
@@ -141,7 +154,100 @@ def parse():
     ap.add_argument('--pmc', default=None,
                     help='rocprofv3 PMC summary for the roofline traffic field (default profiles/pmc_<mode>.json; '
                          'used only when it was captured at this mode and channel count)')
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    if a.dump_outputs and a.mode in ('c1', 'c5bin'):
+        ap.error('--dump-outputs: --mode %s runs the binaries, whose output is their JSON lines' % a.mode)
+    return a
+
+
+DUMP_CHANNELS = 1024  # channels of the dumped sample (all of them when the run has fewer)
+DUMP_LAST = 8         # items kept per sampled channel: its last ones
+DUMP_MSG = 256        # message bytes kept per item
+
+
+class ItemTap:
+    """--dump-outputs: eng.drain_items() for the timed steps that also keeps
+    what it hands back, the ACARS item records (aero_pop_items_all), for a
+    fixed seeded sample of channels.  Which step's drain delivers an item
+    depends on when its pass completed (completed passes are polled, not
+    waited for), so the items of one step alone differ from run to run; the
+    dump takes, per sampled channel, the last DUMP_LAST items delivered by
+    the end of the timed region and the number delivered in all of it, which
+    do not.  Arrays (rank 0's channels):
+      acars_channels     f64 [S]        the sampled engine channels
+      acars_item_counts  f64 [S]        items each received in the timed region
+      acars_items        f32 [S, 8, W]  per channel its last items, oldest first,
+                                        zero rows first where it has fewer: the
+                                        bytes of aero_acars_item up to msg, then
+                                        DUMP_MSG bytes of msg; zero past label_len,
+                                        reg_len and msg_len
+      timed_region       f64 [1 + K]    samples processed, then the timed_region
+                                        counters of the result line in key order"""
+
+    def __init__(self, eng, nch, cap=4096):
+        import ctypes
+        import aero_engine as ae
+        self.eng, self.cap, self.ae, self.ctypes = eng, cap, ae, ctypes
+        rng = np.random.default_rng(0xD0)
+        self.channels = np.sort(rng.choice(nch, size=min(nch, DUMP_CHANNELS), replace=False))
+        self.mask = np.zeros(nch, dtype=bool)
+        self.mask[self.channels] = True
+        self.arr, self.chs = (ae.AcarsItem * cap)(), (ctypes.c_int * cap)()
+        self.rows = np.frombuffer(self.arr, dtype=np.uint8).reshape(cap, ctypes.sizeof(ae.AcarsItem))
+        self.chv = np.frombuffer(self.chs, dtype=np.int32)
+        self.width = ae.AcarsItem.msg.offset + DUMP_MSG
+        self.kept = []
+
+    def drain(self):
+        total = 0
+        while True:
+            n = self.ctypes.c_size_t()
+            rc = self.eng.lib.aero_pop_items_all(self.eng.h, self.arr, self.chs, self.cap, self.ctypes.byref(n))
+            if rc != self.ae.AERO_OK:
+                raise self.ae.AeroError(rc, 'aero_pop_items_all')
+            k = n.value
+            total += k
+            m = self.mask[self.chv[:k]]
+            if m.any():
+                self.kept.append((self.chv[:k][m], self.rows[:k, :self.width][m]))
+            if k < self.cap:
+                return total
+
+    def arrays(self):
+        I = self.ae.AcarsItem
+        S = len(self.channels)
+        items = np.zeros((S, DUMP_LAST, self.width), dtype=np.float32)
+        counts = np.zeros(S, dtype=np.float64)
+        if self.kept:
+            ch = np.concatenate([c for c, _ in self.kept])
+            rec = np.concatenate([r for _, r in self.kept])
+            order = np.argsort(ch, kind='stable')  # per channel in delivery order
+            ch, rec = ch[order], rec[order]
+            # bytes past the lengths are unspecified (aero_pop_items_all copies msg_len bytes of msg)
+            msg_len = rec[:, I.msg_len.offset:I.msg_len.offset + 4].copy().view('<u4').ravel()
+            for off, size, ln in ((I.label.offset, I.label.size, rec[:, I.label_len.offset]),
+                                  (I.reg.offset, I.reg.size, rec[:, I.reg_len.offset]),
+                                  (I.msg.offset, DUMP_MSG, msg_len)):
+                part = rec[:, off:off + size]
+                part[np.arange(size)[None, :] >= ln[:, None]] = 0
+            rec[:, I.pad0.offset] = 0
+            lo = np.searchsorted(ch, self.channels, side='left')
+            hi = np.searchsorted(ch, self.channels, side='right')
+            counts[:] = hi - lo
+            for s in range(S):
+                k = min(int(hi[s] - lo[s]), DUMP_LAST)
+                if k:
+                    items[s, DUMP_LAST - k:] = rec[hi[s] - k:hi[s]]
+        return {'acars_channels': self.channels.astype(np.float64), 'acars_item_counts': counts,
+                'acars_items': items}
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), v)
 
 
 def synth_one(M, seconds, seed, k=0, lead_in=0):
@@ -353,7 +459,7 @@ def run_c5(a, rank, world, local):
     mine = [owner[v] == rank for v in range(len(cfg['vfos']))]
     x = tl.c5_wideband(cfg, C5_SECONDS) if rank == 0 else None
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = c5_cpu_baseline(cfg, x[:int(cfg['sample_rate'] * 4.0)], a.cpu_procs or host_cores())
     import torch
     import torch.distributed as dist
@@ -383,14 +489,18 @@ def run_c5(a, rank, world, local):
         ch.run()
         ch.feed(eng, chans)
         eng.run()
-        return eng.drain_items()
+        return tap.drain() if tap else eng.drain_items()
 
+    tap = None
     pre = 16 + a.warmup  # 4 s of audio: every hunter has locked
     for s in range(pre):
         step(s)
     eng.sync()
     ch.sync()
     torch.cuda.synchronize()
+    if a.dump_outputs and rank == 0:
+        eng.drain_items()  # the dump holds the timed region's items only
+        tap = ItemTap(eng, sum(mine))
     eng.timing_reset()
     s0 = eng.samples_processed()
     if use_dist:
@@ -402,12 +512,14 @@ def run_c5(a, rank, world, local):
         items += step(pre + s)
     eng.sync()
     ch.sync()
-    items += eng.drain_items()
+    items += tap.drain() if tap else eng.drain_items()
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     samples = eng.samples_processed() - s0
+    if tap:
+        dump_outputs(a.dump_outputs, dict(tap.arrays(), timed_region=np.array([samples, items], dtype=np.float64)))
     t = torch.tensor([elapsed, float(samples), float(items)], dtype=torch.float64, device='cuda')
     if use_dist:
         tmax = t.clone()
@@ -702,14 +814,15 @@ def main():
     preroll = M.get('preroll', PREROLL_HOPS)  # burst channels have no hunter to lock
     pre = preroll + a.warmup  # untimed hops: lock-in pre-roll + warmup
     burst = bool(M.get('burst'))
-    h2d_steps = 0 if burst else max(0, a.steps if a.h2d_steps is None else a.h2d_steps)
+    # the H2D-inclusive second region is a measurement of its own: --full
+    h2d_steps = 0 if burst or not a.full else max(0, a.steps if a.h2d_steps is None else a.h2d_steps)
     steps_total = pre + a.steps + h2d_steps
     span = steps_total * HOP
     offsets = shard.channel_offsets(C, P, rank)
     pool_host = make_pool(M, P, span + int(offsets.max()) + 1, 0xAE20 + 1000 * rank)
-    # CPU baseline first, in worker processes forked before this process touches the GPU
+    # CPU baseline (--full) first, in worker processes forked before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         # the oracle runs what the GPU runs: the DCD timer on the P channel unless --no-dcd-tick
         Mc = dict(M, dcd_tick=M['bitrate'] == 10500 and not M.get('burst') and not a.no_dcd_tick)
         cpu = cpu_baseline(a.mode, Mc, a.cpu_seconds or M['cpu_seconds'], a.cpu_procs or host_cores(), a.cpu_runs)
@@ -745,6 +858,8 @@ def main():
     eng.timing_reset()
     s0 = eng.samples_processed()
     st0 = {k: eng.stat(k) for k in stat_names}
+    tap = ItemTap(eng, C) if a.dump_outputs and rank == 0 else None
+    drain = tap.drain if tap else eng.drain_items
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -753,10 +868,10 @@ def main():
     for x in timed_inputs:
         eng.push_batch_device(x.data_ptr(), HOP, C, C)
         eng.run()
-        items += eng.drain_items()  # ACARS items leave every step, as a serving host would take them
+        items += drain()  # ACARS items leave every step, as a serving host would take them
     t_tail = time.perf_counter()
     eng.sync()
-    items += eng.drain_items()
+    items += drain()
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -824,6 +939,9 @@ def main():
         del host_inputs
     stats['acars_items'] = items
     keys = sorted(stats)
+    if tap:
+        dump_outputs(a.dump_outputs, dict(tap.arrays(), timed_region=np.array(
+            [samples] + [stats[k] for k in keys], dtype=np.float64)))
     t = torch.tensor([elapsed, float(samples)] + [float(stats[k]) for k in keys], dtype=torch.float64,
                      device='cuda')
     if use_dist:

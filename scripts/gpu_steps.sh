@@ -5,7 +5,7 @@
 #   tests[=K_EXPR]     the GPU suite (or a -k subset; '+' stands for ' or ')
 #   vtests=VARIANT:K   a -k subset of the GPU suite on libaero_engine_VARIANT.so
 #   smoke              __graft_entry__.smoke()
-#   bench[=ARGS]       bench.py (default: the headline line), ARGS comma-separated
+#   bench[=ARGS]       bench.py --full (or the plain run with ARGS, comma-separated)
 #   mode=M             bench.py --mode M with its CPU baseline (one run)
 #   ab=VARIANT:M       bench.py --mode M on libaero_engine_VARIANT.so, no CPU baseline
 #   env=VAR=VALUE      export VAR=VALUE for the steps after it
@@ -36,9 +36,9 @@ for st in "$@"; do
     vtests=*) v=${st#vtests=}; k=${v#*:}; v=${v%%:*}
       AERO_ENGINE_SO=$R/aero-cli_amd/libaero_engine_$v.so step 900 pytest_gpu_${v}_${k//+/_}.log python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu -k "${k//+/ or }" tests ;;
     smoke) step 300 smoke.log python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step 400 bench.log python bench.py ;;
+    bench) step 400 bench.log python bench.py --full ;;
     bench=*) a=${st#bench=}; step 400 "bench_${a//[ ,=-]/_}.log" python bench.py ${a//,/ } ;;
-    mode=*) m=${st#mode=}; step 400 bench_$m.log python bench.py --mode $m --cpu-runs 1 ;;
+    mode=*) m=${st#mode=}; step 400 bench_$m.log python bench.py --full --mode $m --cpu-runs 1 ;;
     ab=*) v=${st#ab=}; m=${v#*:}; v=${v%%:*}
       so=$R/aero-cli_amd/libaero_engine${v:+_$v}.so; [ "$v" = prod ] && so=$R/aero-cli_amd/libaero_engine.so
       AERO_ENGINE_SO=$so step 300 bench_${m}_$v${GPU_MAX_HW_QUEUES:+_q$GPU_MAX_HW_QUEUES}.log python bench.py --mode $m --no-cpu-baseline ;;

@@ -17,7 +17,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "$PART" = a ]; then
-  timeout -k 10 480 python3 $R/bench.py --steps 20 --warmup 5 > $OUT/bench.log 2>&1
+  timeout -k 10 480 python3 $R/bench.py --full --steps 20 --warmup 5 > $OUT/bench.log 2>&1
   timeout -k 10 480 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o prof -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_prof.log 2>&1
   find /tmp/prof_$TAG -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats.csv \;
   for c in FETCH_SIZE WRITE_SIZE; do
@@ -32,16 +32,16 @@ if [ "$PART" = a ]; then
   python3 $R/tools/pmc_json.py $OUT/pmc_FETCH_SIZE.csv $OUT/pmc_WRITE_SIZE.csv $OUT/pmc_oqpsk10500.json oqpsk10500 65536 \
     "rocprofv3 --pmc, one pass per counter, bench.py --steps 4 --warmup 1 (65536 channels, after the 48-hop pre-roll; averages over every dispatch of the run), profiles/$TAG/pmc_{FETCH,WRITE}_SIZE.csv" > /dev/null
 elif [ "$PART" = b ]; then
-  timeout -k 10 600 python3 $R/bench.py --mode burst10500 --steps 10 --cpu-runs 1 > $OUT/bench_burst.log 2>&1
+  timeout -k 10 600 python3 $R/bench.py --full --mode burst10500 --steps 10 --cpu-runs 1 > $OUT/bench_burst.log 2>&1
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/profb_$TAG -o prof -- python3 $R/bench.py --mode burst10500 --steps 6 --no-cpu-baseline > $OUT/bench_burst_prof.log 2>&1
   find /tmp/profb_$TAG -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats_burst.csv \;
-  timeout -k 10 600 python3 $R/bench.py --mode burstmsk1200 --steps 6 --cpu-runs 1 > $OUT/bench_burstmsk.log 2>&1
+  timeout -k 10 600 python3 $R/bench.py --full --mode burstmsk1200 --steps 6 --cpu-runs 1 > $OUT/bench_burstmsk.log 2>&1
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/profm_$TAG -o prof -- python3 $R/bench.py --mode burstmsk1200 --steps 4 --no-cpu-baseline > $OUT/bench_burstmsk_prof.log 2>&1
   find /tmp/profm_$TAG -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats_burstmsk.csv \;
 else
-  timeout -k 10 400 python3 $R/bench.py --mode msk600 --steps 20 --cpu-runs 1 > $OUT/bench_msk600.log 2>&1
-  timeout -k 10 400 python3 $R/bench.py --mode msk1200 --steps 20 --cpu-runs 1 > $OUT/bench_msk1200.log 2>&1
-  timeout -k 10 400 python3 $R/bench.py --mode c5 --steps 20 > $OUT/bench_c5.log 2>&1
+  timeout -k 10 400 python3 $R/bench.py --full --mode msk600 --steps 20 --cpu-runs 1 > $OUT/bench_msk600.log 2>&1
+  timeout -k 10 400 python3 $R/bench.py --full --mode msk1200 --steps 20 --cpu-runs 1 > $OUT/bench_msk1200.log 2>&1
+  timeout -k 10 400 python3 $R/bench.py --full --mode c5 --steps 20 > $OUT/bench_c5.log 2>&1
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/profc_$TAG -o prof -- python3 $R/bench.py --mode c5 --steps 20 --no-cpu-baseline > $OUT/bench_c5_prof.log 2>&1
   find /tmp/profc_$TAG -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats_c5.csv \;
   timeout -k 10 400 python3 $R/bench.py --mode c5bin --steps 3 > $OUT/bench_c5bin.log 2>&1

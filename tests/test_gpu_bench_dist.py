@@ -28,7 +28,7 @@ def _bench(args, timeout):
 
 
 def test_bench_rccl_group_c2():
-    out = _bench(['--channels', '4096', '--steps', '3', '--warmup', '1', '--h2d-steps', '1'], 240)
+    out = _bench(['--full', '--channels', '4096', '--steps', '3', '--warmup', '1', '--h2d-steps', '1'], 240)
     assert out['process_group'] == 'nccl' and out['n_gpus'] == 1
     assert out['config']['total_channels'] == 4096
     assert out['value'] > 0 and out['h2d']['value'] > 0
