@@ -90,6 +90,8 @@ _SIGS = {
     'aero_engine_create': (ctypes.c_int, [ctypes.POINTER(EngineCfg), ctypes.POINTER(ctypes.c_void_p)]),
     'aero_engine_destroy': (None, [ctypes.c_void_p]),
     'aero_channel_open': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ChannelCfg), ctypes.POINTER(ctypes.c_int)]),
+    'aero_channel_close': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'aero_engine_reserve': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ChannelCfg), ctypes.c_int]),
     'aero_push_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                      ctypes.c_uint32]),
     'aero_push_pcm_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
@@ -272,6 +274,19 @@ class Engine:
         self._fs[ch.value] = fs
         return ch.value
 
+    def close_channel(self, ch):
+        """aero_channel_close: drops the channel's pending samples and
+        undelivered outputs; its id and slot go to the next open_channel."""
+        _check(self.lib.aero_channel_close(self.h, ch), 'aero_channel_close')
+        self._fs.pop(ch, None)
+
+    def reserve(self, n, bitrate=10500, fs=None, burst=False):
+        """aero_engine_reserve: the kind's group is created with n slots
+        instead of max_channels (before the kind's first open_channel)."""
+        fs = fs or self.RATE.get(bitrate, 48000)
+        cfg = ChannelCfg(bitrate, int(burst), fs, 0)
+        _check(self.lib.aero_engine_reserve(self.h, ctypes.byref(cfg), n), 'aero_engine_reserve')
+
     def push(self, ch, pcm, fs=None):
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         fs = fs or self._fs.get(ch, 48000)
@@ -406,7 +421,7 @@ class Engine:
 
     def stat(self, name):
         """aero_stat counter: 'viterbi_jobs', 'frames', 'su_crc_ok' (and burst 'rt_*'), or the
-        continuous groups' 'device_bytes' / 'groups'."""
+        continuous groups' 'device_bytes' / 'groups', or 'slot_resets' (reset-kernel launches)."""
         v = ctypes.c_uint64()
         _check(self.lib.aero_stat(self.h, name.encode(), ctypes.byref(v)), 'aero_stat')
         return int(v.value)

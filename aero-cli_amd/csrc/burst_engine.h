@@ -15,6 +15,13 @@ enum BurstKind { BURST_OQPSK = 0, BURST_MSK = 1 };  // 10500 OQPSK / 600-1200 MS
 int burst_group_create(int device, int flags, int max_channels, int kind, BurstGroup **out);
 void burst_group_destroy(BurstGroup *g);
 int burst_open(BurstGroup *g, int bitrate, bool disable_reassembly, int *local);
+// closes local channel c: its pending samples and undelivered outputs are
+// dropped, its slot is reset (one kernel launch for every slot closed or
+// reopened since, at the group's next push or run) and reused by burst_open,
+// the smallest free slot first
+int burst_close(BurstGroup *g, int c);
+struct LayoutRec;
+size_t burst_layout_plan(int kind, int C, LayoutRec *rec);  // slot_reset.h: the pool's arrays; returns the pool size
 int burst_push(BurstGroup *g, int c, const int16_t *pcm, size_t n, bool dev, bool msg_start);
 int burst_push_batch(BurstGroup *g, const int16_t *src, size_t n, size_t ld, int nch, bool dev);
 int burst_run(BurstGroup *g, int flush);
@@ -25,7 +32,7 @@ int burst_pop_tests(BurstGroup *g, int c, uint8_t *dst, size_t cap, size_t *n);
 int burst_pop_packets(BurstGroup *g, int c, uint8_t *dst, size_t cap, size_t *n);
 std::vector<aero_acars_item> &burst_items(BurstGroup *g, int c);
 uint64_t burst_processed(const BurstGroup *g);
-uint64_t burst_stat(const BurstGroup *g, int which);  // 0: R/T tests run, 1: R/T packets decoded, 2: most tests of one pass
+uint64_t burst_stat(const BurstGroup *g, int which);  // 0: R/T tests run, 1: R/T packets decoded, 2: most tests of one pass, 3: reset-kernel launches
 int burst_dcd_edges(BurstGroup *g, int c, int64_t *edges);  // AeroL datacd changes (waits for the group's work)
 void burst_timing(BurstGroup *g, const char *name, double *ms, long *launches);  // adds to *ms / *launches
 void burst_timing_reset(BurstGroup *g);

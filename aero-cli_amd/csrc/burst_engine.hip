@@ -21,6 +21,7 @@
 #include <memory>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/aero_engine.h"
@@ -29,6 +30,7 @@
 #include "burst_engine.h"
 #include "engine_common.h"
 #include "host_pool.h"
+#include "slot_reset.h"
 #include "tables_host.h"
 
 namespace aero {
@@ -46,6 +48,9 @@ void launch_front_bmsk(hipStream_t st, const BurstState &S, const BurstTables &T
 void launch_demod_bmsk(hipStream_t st, const BurstState &S, const BurstTables &T, int nch, int trace);
 void launch_trident_bmsk(hipStream_t st, const BurstState &S, const BurstTables &T, int nch);
 void launch_frame_bmsk(hipStream_t st, const BurstState &S, int nch);
+// slot_reset.hip
+void launch_reset_slots(hipStream_t, void *, const ResetSeg *, int, const int *, const int *, int, const ResetInit *,
+                        unsigned long long);
 
 namespace {
 
@@ -102,13 +107,6 @@ __global__ void b_batch_counts_kernel(long long *ls, long long *chunks, int C, i
   chunks[(size_t)j * CHUNK_RING + (k & (CHUNK_RING - 1))] = start;
   ls[(size_t)BL_CHUNK_N * C + j] = k + 1;
   ls[(size_t)BL_AVAIL * C + j] = start + n;
-}
-
-template <class T>
-T *carve(char *&p, size_t count) {
-  T *r = reinterpret_cast<T *>(p);
-  p += (count * sizeof(T) + 255) & ~size_t(255);
-  return r;
 }
 
 // AeroLcrc16::calcusingbitsandcheck (decode/aerol.h:273-307)
@@ -182,67 +180,99 @@ struct BurstGroup {
   std::vector<double> init_ds;  // [field][channel - init_lo]
   std::vector<int> init_is;
   std::vector<int> since_run;      // messages pushed since the last run (message-start ring)
+  // slots closed channels left (burst_close), the smallest reused first by
+  // burst_open; reset_pending: slot -> scalar-init index of those whose device
+  // state awaits the reset kernel (burst_flush_reset)
+  std::vector<int> free_slots;
+  std::vector<uint8_t> is_free;
+  std::map<int, int> reset_pending;
+  std::vector<ResetSeg> reset_plan;
+  ResetSeg *d_reset_plan = nullptr;
+  ResetInit *d_reset_init = nullptr;  // [2]: 600 bps MSK or OQPSK, 1200 bps MSK
+  int *d_reset_slots = nullptr;       // [2][C]: slots, scalar-init index
+  bool reset_ready = false;
+  uint64_t reset_launches = 0;        // aero_stat "slot_resets"
 };
 
 namespace {
 
-size_t burst_layout(int kind, BurstState &S, BurstTables &T, int C, char *base, double2 **hk_out) {
+// The pool layout.  Every array goes through carve() (slot_reset.h), which
+// notes in `rec` how a channel's part of it is addressed: the per-channel
+// entries are the reset plan of a slot (burst_flush_reset, burst_layout_plan).
+size_t burst_layout(int kind, BurstState &S, BurstTables &T, int C, char *base, double2 **hk_out,
+                    LayoutRec *rec = nullptr) {
   const bool msk = kind == BURST_MSK;
   char *p = base;
+  if (rec) rec->C = C;
+  const size_t Cz = (size_t)C;
+  // time-major [rows][C] of `per` elements / channel-major [C][len] / no slot's
+  auto col = [&](auto *&dst, size_t rows, size_t per = 1, int fill = RF_ZERO) {
+    using E = std::remove_pointer_t<std::remove_reference_t<decltype(dst)>>;
+    dst = carve<E>(p, base, rows * per * Cz, rec, RS_COL, per * sizeof(E), rows, fill);
+  };
+  auto row = [&](auto *&dst, size_t len) {
+    using E = std::remove_pointer_t<std::remove_reference_t<decltype(dst)>>;
+    dst = carve<E>(p, base, len * Cz, rec, RS_ROW, len * sizeof(E));
+  };
+  auto shared = [&](auto *&dst, size_t count) {
+    using E = std::remove_const_t<std::remove_pointer_t<std::remove_reference_t<decltype(dst)>>>;
+    dst = carve<E>(p, base, count, rec);
+  };
   S.C = C;
-  S.hop_n = carve<int>(p, (size_t)C);
-  S.ds = carve<double>(p, (size_t)BURST_DS_COUNT * C);
-  S.is = carve<int>(p, (size_t)BURST_IS_COUNT * C);
-  S.ls = carve<long long>(p, (size_t)BL_COUNT * C);
-  S.fir = carve<double>(p, (size_t)2 * (msk ? M_NT : NTAPS) * C);
-  S.ana = carve<double2>(p, (size_t)ANA_LEN * C);
-  S.pcm = carve<int16_t>(p, (size_t)B_PCM_CAP * C);
+  row(S.hop_n, 1);
+  col(S.ds, BURST_DS_COUNT, 1, RF_DS);
+  col(S.is, BURST_IS_COUNT, 1, RF_IS);
+  col(S.ls, BL_COUNT);
+  col(S.fir, (size_t)2 * (msk ? M_NT : NTAPS));
+  col(S.ana, (size_t)ANA_LEN >> ANA_LB, (size_t)1 << ANA_LB);  // runs of 2^ANA_LB samples (ana_idx)
+  row(S.pcm, (size_t)B_PCM_CAP);
   S.pcm_cap = B_PCM_CAP;
-  S.hb_rem = carve<double2>(p, (size_t)HB_REM * C);
-  S.agc = carve<double>(p, (size_t)B_AGC * C);
-  S.agc2 = carve<double>(p, (size_t)(msk ? M_AGC2 : B_AGC2) * C);
-  S.d1 = carve<double>(p, (size_t)(msk ? M_D1 : B_D1) * C);
-  S.vring = carve<double>(p, (size_t)(msk ? MV_LEN : BV_LEN) * C);
-  S.ma1 = carve<double2>(p, (size_t)(msk ? M_MA : B_MA) * C);
-  S.mav1 = carve<double>(p, (size_t)(msk ? M_MA : B_MA) * C);
+  row(S.hb_rem, (size_t)HB_REM);
+  col(S.agc, (size_t)B_AGC);
+  col(S.agc2, (size_t)(msk ? M_AGC2 : B_AGC2));
+  col(S.d1, (size_t)(msk ? M_D1 : B_D1));
+  col(S.vring, (size_t)(msk ? MV_LEN : BV_LEN));
+  col(S.ma1, (size_t)(msk ? M_MA : B_MA));
+  col(S.mav1, (size_t)(msk ? M_MA : B_MA));
   if (msk) {  // bt_d1 (complex), bt_ma_diff, a1, delayt8, delayedsmpl (complex)
-    const int sz[5] = {2 * M_BTD, M_MADIFF, M_A1, M_D8, 2 * M_DSM};
-    for (int k = 0; k < 5; k++) S.dl[k] = carve<double>(p, (size_t)sz[k] * C);
+    const int sz[5] = {M_BTD, M_MADIFF, M_A1, M_D8, M_DSM};
+    for (int k = 0; k < 5; k++) col(S.dl[k], (size_t)sz[k], k == 0 || k == 4 ? 2 : 1);
+    for (int k = 5; k < BDL_COUNT; k++) S.dl[k] = nullptr;
   } else {
     for (int k = 0; k < BDL_COUNT; k++)  // sizes <= 1172 (bt_ma_diff); BDL_BT holds double2
-      S.dl[k] = carve<double>(p, (size_t)(k == BDL_BT ? 2 : 1) * 1172 * C);
+      col(S.dl[k], 1172, k == BDL_BT ? 2 : 1);
   }
-  S.pd3 = carve<double>(p, (size_t)(msk ? M_PD3 : B_PD3) * C);
-  S.tri = carve<double>(p, (size_t)TRI_SLOTS * (msk ? M_TRI : B_TRI) * C);
-  S.chk_n = carve<long long>(p, (size_t)TRI_SLOTS * C);
-  S.chk = carve<double>(p, (size_t)TRI_SLOTS * CHK_REC * C);
-  S.tjobs = carve<int>(p, (size_t)TRI_SLOTS * C);
-  S.ntjobs = carve<int>(p, 16);
-  S.msema = carve<double>(p, (size_t)(msk ? M_MSEMA : B_MSEMA) * C);
-  S.chunks = carve<long long>(p, (size_t)CHUNK_RING * C);
-  S.soft = carve<int16_t>(p, (size_t)B_SOFT_RING * C);
+  col(S.pd3, (size_t)(msk ? M_PD3 : B_PD3));
+  row(S.tri, (size_t)TRI_SLOTS * (msk ? M_TRI : B_TRI));
+  row(S.chk_n, (size_t)TRI_SLOTS);
+  row(S.chk, (size_t)TRI_SLOTS * CHK_REC);
+  shared(S.tjobs, (size_t)TRI_SLOTS * C);
+  shared(S.ntjobs, 16);
+  row(S.msema, (size_t)(msk ? M_MSEMA : B_MSEMA));
+  row(S.chunks, (size_t)CHUNK_RING);
+  row(S.soft, (size_t)B_SOFT_RING);
   S.hop_cap = B_HOP_CAP;
-  S.hops = carve<double>(p, (size_t)B_HOP_CAP * 6 * C);
-  S.rtblock = carve<uint8_t>(p, (size_t)RT_BLOCK * C);
-  S.jobs = carve<int>(p, (size_t)4 * RT_TESTS_PER_PASS * C);
-  S.njobs = carve<int>(p, 16);
-  S.jobout = carve<uint8_t>(p, (size_t)RT_JOB_OUT * RT_TESTS_PER_PASS * C);
-  S.tri_abs = carve<double>(p, (size_t)(msk ? 1 : TRI_N) * TRI_GRID);
-  T.cis = carve<double2>(p, WTSIZE);
-  T.tw8 = carve<double2>(p, 8192);
-  T.twi8 = carve<double2>(p, 8192);
-  T.tw16 = carve<double2>(p, 16384);
-  double2 *hk = carve<double2>(p, HB_N);
+  row(S.hops, (size_t)B_HOP_CAP * 6);
+  row(S.rtblock, (size_t)RT_BLOCK);
+  shared(S.jobs, (size_t)4 * RT_TESTS_PER_PASS * C);
+  shared(S.njobs, 16);
+  shared(S.jobout, (size_t)RT_JOB_OUT * RT_TESTS_PER_PASS * C);
+  shared(S.tri_abs, (size_t)(msk ? 1 : TRI_N) * TRI_GRID);
+  shared(T.cis, WTSIZE);
+  shared(T.tw8, 8192);
+  shared(T.twi8, 8192);
+  shared(T.tw16, 16384);
+  double2 *hk = carve<double2>(p, base, HB_N, rec);
   T.hk = hk;
   if (hk_out) *hk_out = hk;
-  T.hk_time = carve<double2>(p, HB_N);
-  T.da = carve<double2>(p, TRI_N);
-  T.db = carve<double2>(p, TRI_N);
-  T.taps = carve<double>(p, 128);
+  shared(T.hk_time, HB_N);
+  shared(T.da, TRI_N);
+  shared(T.db, TRI_N);
+  shared(T.taps, 128);
   for (int k = 0; k < BDL_COUNT; k++) {
-    T.dw[k] = carve<double>(p, 1172);
-    T.domw[k] = carve<double>(p, 1172);
-    T.dio[k] = carve<int>(p, 1172);
+    shared(T.dw[k], 1172);
+    shared(T.domw[k], 1172);
+    shared(T.dio[k], 1172);
   }
   return (size_t)(p - base);
 }
@@ -572,18 +602,19 @@ void burst_group_destroy(BurstGroup *g) {
   if (!g) return;
   if (g->st) (void)hipStreamSynchronize(g->st);
   if (g->d_scratch) (void)hipFree(g->d_scratch);
+  if (g->d_reset_plan) (void)hipFree(g->d_reset_plan);
+  if (g->d_reset_init) (void)hipFree(g->d_reset_init);
+  if (g->d_reset_slots) (void)hipFree(g->d_reset_slots);
   if (g->pool) (void)hipFree(g->pool);
   if (g->st) (void)hipStreamDestroy(g->st);
   delete g;
 }
 
-int burst_open(BurstGroup *g, int bitrate, bool disable_reassembly, int *local) {
-  if (g->nch >= g->C) return AERO_E_FULL;
-  const int c = g->nch;
-  const int C = g->C;
-  std::vector<double> ds(BURST_DS_COUNT, 0.0);
-  std::vector<int> is(BURST_IS_COUNT, 0);
-  if (g->kind == BURST_MSK) {
+// scalar state of a new channel
+static int burst_scalar_init(int kind, int bitrate, std::vector<double> &ds, std::vector<int> &is) {
+  ds.assign(BURST_DS_COUNT, 0.0);
+  is.assign(BURST_IS_COUNT, 0);
+  if (kind == BURST_MSK) {
     if (bitrate != 600 && bitrate != 1200) return AERO_E_INVALID;
     // BurstMskDemodulator ctor + setSettings (burstmskdemodulator.cpp:9-297):
     // mixer2 at freq_center 1000, st_osc / st_osc_half at fb / 2; AeroL MSK
@@ -616,9 +647,47 @@ int burst_open(BurstGroup *g, int bitrate, bool disable_reassembly, int *local) 
     is[BI_STARTSTOP] = -1;
     is[BI_FCNTR] = 1000000000;
   }
+  return AERO_OK;
+}
+
+// host mirrors of slot c as burst_open leaves a new channel's
+static void burst_host_reset(BurstGroup *g, int c, bool disable_reassembly) {
+  g->avail[c] = 0;
+  g->chunk_n[c] = 0;
+  g->host[c].reset(new PChannelHost(disable_reassembly));
+  g->ok_burst[c] = -1;
+  g->soft_hold[c].clear();
+  g->soft_seen[c] = 0;
+  g->hop_hold[c].clear();
+  g->hops_seen[c] = 0;
+  g->tests_hold[c].clear();
+  g->packets_hold[c].clear();
+  g->hb_base[c] = 0;
+  g->since_run[c] = 0;
+  g->tsu[c] = 0;
+  g->tblocks[c] = 0;
+}
+
+int burst_open(BurstGroup *g, int bitrate, bool disable_reassembly, int *local) {
+  std::vector<double> ds;
+  std::vector<int> is;
+  if (int rc = burst_scalar_init(g->kind, bitrate, ds, is)) return rc;
+  if (!g->free_slots.empty()) {
+    // the smallest slot a closed channel left; its device state goes through
+    // the reset kernel with this channel's scalar init (burst_flush_reset)
+    const auto it = std::min_element(g->free_slots.begin(), g->free_slots.end());
+    const int c = *it;
+    g->free_slots.erase(it);
+    g->is_free[c] = 0;
+    burst_host_reset(g, c, disable_reassembly);
+    g->reset_pending[c] = bitrate == 1200 ? 1 : 0;
+    *local = c;
+    return AERO_OK;
+  }
+  if (g->nch >= g->C) return AERO_E_FULL;
+  const int c = g->nch;
   // the device copy waits for the next push or run (flush_init): one copy per
   // field for every channel opened since, not one per field per channel
-  (void)C;
   g->init_ds.insert(g->init_ds.end(), ds.begin(), ds.end());
   g->init_is.insert(g->init_is.end(), is.begin(), is.end());
   g->nch++;
@@ -636,14 +705,91 @@ int burst_open(BurstGroup *g, int bitrate, bool disable_reassembly, int *local) 
   g->since_run.push_back(0);
   g->tsu.push_back(0);
   g->tblocks.push_back(0);
+  g->is_free.push_back(0);
   *local = c;
   return AERO_OK;
 }
 
-// initial device state of the channels opened since the last push or run
+// The slots of closed channels back to a new channel's state: one launch of
+// the reset kernel (slot_reset.hip) for every slot queued since the last push
+// or run: every per-channel array of burst_layout() zeroed, as the zeroed
+// pool leaves a slot never used, and burst_open's scalar init.
+static int burst_flush_reset(BurstGroup *g) {
+  if (g->reset_pending.empty()) return AERO_OK;
+  const int n = (int)g->reset_pending.size(), C = g->C;
+  if (!g->reset_ready) {
+    LayoutRec rec;
+    BurstState S{};
+    BurstTables T{};
+    burst_layout(g->kind, S, T, C, nullptr, nullptr, &rec);
+    const std::vector<ResetSeg> plan = reset_plan(rec);
+    if (rec.bad || BURST_DS_COUNT > RESET_DS_MAX || BURST_IS_COUNT > RESET_IS_MAX) return AERO_E_INVALID;
+    ResetInit init[2] = {};
+    for (int v = 0; v < 2; v++) {
+      std::vector<double> ds;
+      std::vector<int> is;
+      if (int rc = burst_scalar_init(g->kind, g->kind == BURST_MSK ? (v ? 1200 : 600) : 10500, ds, is)) return rc;
+      std::copy(ds.begin(), ds.end(), init[v].ds);
+      std::copy(is.begin(), is.end(), init[v].is);
+    }
+    // (a call that failed half way left what it had allocated: kept, the rest made now)
+    if (!g->d_reset_plan && hipMalloc(&g->d_reset_plan, sizeof(ResetSeg) * plan.size()) != hipSuccess)
+      return AERO_E_NOMEM;
+    if (!g->d_reset_init && hipMalloc(&g->d_reset_init, sizeof init) != hipSuccess) return AERO_E_NOMEM;
+    if (!g->d_reset_slots && hipMalloc(&g->d_reset_slots, sizeof(int) * 2 * C) != hipSuccess) return AERO_E_NOMEM;
+    BCHK(hipMemcpy(g->d_reset_plan, plan.data(), sizeof(ResetSeg) * plan.size(), hipMemcpyHostToDevice));
+    BCHK(hipMemcpy(g->d_reset_init, init, sizeof init, hipMemcpyHostToDevice));
+    g->reset_plan = plan;
+    g->reset_ready = true;  // only now: every buffer exists and is filled
+  }
+  std::vector<int> list((size_t)2 * C, 0);
+  int i = 0;
+  for (const auto &sv : g->reset_pending) {  // (a map: sorted by slot)
+    if (sv.first < 0 || sv.first >= C) return AERO_E_INVALID;
+    list[i] = sv.first;
+    list[C + i] = sv.second;
+    i++;
+  }
+  // the group's stream is idle between its calls (every push and run ends
+  // with a wait), so the previous launch has read its list; this copy is
+  // done when it returns
+  BCHK(hipMemcpy(g->d_reset_slots, list.data(), sizeof(int) * 2 * C, hipMemcpyHostToDevice));
+  launch_reset_slots(g->st, g->pool, g->d_reset_plan, (int)g->reset_plan.size(), g->d_reset_slots,
+                     g->d_reset_slots + C, n, g->d_reset_init, reset_items(g->reset_plan, n));
+  BCHK(hipGetLastError());
+  g->reset_launches++;
+  g->reset_pending.clear();
+  return AERO_OK;
+}
+
+// A channel leaves: what it pushed and has not run, and what it produced and
+// has not popped, is dropped.  The slot's device state is reset before the
+// group's next push or run (so the samples still pending are never
+// demodulated) and the slot goes to the next burst_open.
+int burst_close(BurstGroup *g, int c) {
+  if (!g || c < 0 || c >= g->nch || g->is_free[c]) return AERO_E_INVALID;
+  BCHK(hipSetDevice(g->device));
+  BCHK(hipStreamSynchronize(g->st));
+  burst_host_reset(g, c, false);
+  g->is_free[c] = 1;
+  g->free_slots.push_back(c);
+  g->reset_pending[c] = 0;
+  return AERO_OK;
+}
+
+// the recorded layout of a pool of C channels, for the host check (no GPU)
+size_t burst_layout_plan(int kind, int C, LayoutRec *rec) {
+  BurstState S{};
+  BurstTables T{};
+  return burst_layout(kind, S, T, C, nullptr, nullptr, rec);
+}
+
+// initial device state of the channels opened since the last push or run,
+// then the reset of the slots closed since (a slot both opened and closed
+// since gets the reset's state)
 static int flush_init(BurstGroup *g) {
   const int n = g->nch - g->init_lo;
-  if (n <= 0) return AERO_OK;
+  if (n <= 0) return burst_flush_reset(g);
   std::vector<double> col(n);
   std::vector<int> icol(n);
   for (int f = 0; f < BURST_DS_COUNT; f++) {
@@ -657,7 +803,7 @@ static int flush_init(BurstGroup *g) {
   g->init_lo = g->nch;
   g->init_ds.clear();
   g->init_is.clear();
-  return AERO_OK;
+  return burst_flush_reset(g);
 }
 
 int burst_run(BurstGroup *g, int flush) {
@@ -820,6 +966,7 @@ int burst_dcd_edges(BurstGroup *g, int c, int64_t *edges) {
 
 uint64_t burst_stat(const BurstGroup *g, int which) {
   if (!g) return 0;
+  if (which == 3) return g->reset_launches;
   return which == 2 ? g->st_pass_max : (which ? g->st_packets : g->st_tests);
 }
 void burst_timing(BurstGroup *g, const char *name, double *ms, long *launches) {

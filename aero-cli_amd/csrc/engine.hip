@@ -28,7 +28,9 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <set>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/aero_engine.h"
@@ -39,6 +41,7 @@
 #include "fft_layout.h"
 #include "host_pool.h"
 #include "engine_internal.h"
+#include "slot_reset.h"
 #include "tables_host.h"
 
 namespace aero {
@@ -59,6 +62,9 @@ void launch_prefilter_c(hipStream_t, const DevState &, const DevTables &, const 
 void launch_demod_c(hipStream_t, const DevState &, const DevTables &, int, bool);
 void upload_c_constants(const DelayDesc *);
 int c_prejob_bytes();
+// slot_reset.hip
+void launch_reset_slots(hipStream_t, void *, const ResetSeg *, int, const int *, const int *, int, const ResetInit *,
+                        unsigned long long);
 }  // namespace aero
 
 using namespace aero;
@@ -194,6 +200,16 @@ struct Group {
   // local slots an MSK channel left for another rate's group (msk_migrate),
   // reused by the next channel added to this group (group_add_channel)
   std::vector<int> free_slots;
+  // freed slots whose device state awaits the reset kernel (flush_pending_reset)
+  std::vector<int> reset_pending;
+  std::vector<uint8_t> reset_wait;  // per slot: on reset_pending (its device state is the closed channel's)
+  std::vector<ResetSeg> reset_plan;
+  ResetSeg *d_reset_plan = nullptr;
+  ResetInit *d_reset_init = nullptr;
+  int *d_reset_slots = nullptr, *pin_reset_slots = nullptr;  // [2][C]: slots, scalar-init index
+  hipEvent_t reset_ev = nullptr;  // after the last reset launch
+  bool reset_done = false, reset_ready = false;
+  uint64_t reset_launches = 0;  // aero_stat "slot_resets"
   // host mirrors of the per-channel counters
   std::vector<long long> avail, nsamp, hops;
   std::vector<std::unique_ptr<PChannelHost>> host;
@@ -315,74 +331,114 @@ struct aero_engine {
   // by gid: the fixed kinds (Mode), GID_C8400, then generic-rate MSK groups
   std::vector<std::unique_ptr<Group>> groups = std::vector<std::unique_ptr<Group>>(MODE_COUNT + 1);
   BurstGroup *burst[2] = {nullptr, nullptr};  // BURST_OQPSK, BURST_MSK
-  std::vector<std::pair<int, int>> chmap;  // engine channel -> (gid or MODE_BURST + kind, local index)
+  // engine channel -> (gid or MODE_BURST + kind, local index); (-1, -1): closed, its id in free_ids
+  std::vector<std::pair<int, int>> chmap;
+  std::set<int> free_ids;
+  // aero_engine_reserve: channels a kind's group is created for, by (gid,
+  // MODE_BURST + kind or generic-rate Mode, the generic rate's fs or 0)
+  std::map<std::pair<int, int>, int> reserved;
+  int capacity(int key, int fs) const {
+    auto it = reserved.find({key, fs});
+    return it == reserved.end() ? max_channels : it->second;
+  }
   std::unique_ptr<HostPool> hpool;
   std::map<std::string, TimingSlot> timing;  // engine-level host sections
-  uint64_t retired_jobs = 0, retired_frames = 0, retired_su_ok = 0;  // counters of released groups
+  uint64_t retired_jobs = 0, retired_frames = 0, retired_su_ok = 0, retired_resets = 0;  // counters of released groups
 };
 
 namespace {
 
-template <class T>
-T *carve(char *&p, size_t count) {
-  T *r = reinterpret_cast<T *>(p);
-  size_t b = (count * sizeof(T) + 255) & ~size_t(255);
-  p += b;
-  return r;
-}
-
-size_t layout(DevState &S, DevTables &T, int mode, const ModeGeom &g, int C, int flags, char *base) {
+// The pool layout.  Every array goes through carve() (slot_reset.h), which
+// notes in `rec` how a channel's part of it is addressed: the per-channel
+// entries are the reset plan of a slot (group_reset_plan, aero_x_reset_plan).
+size_t layout(DevState &S, DevTables &T, int mode, const ModeGeom &g, int C, int flags, char *base,
+              LayoutRec *rec = nullptr) {
   const bool msk = mode != MODE_OQPSK && mode != MODE_C8400;
   char *p = base;
+  if (rec) rec->C = C;
+  const size_t Cz = (size_t)C;
+  // time-major [rows][C] / channel-major [C][bytes] / no slot's (tables, job lists, placeholders)
+  auto col = [&](auto *&dst, size_t rows, int fill = RF_ZERO) {
+    using E = std::remove_pointer_t<std::remove_reference_t<decltype(dst)>>;
+    dst = carve<E>(p, base, rows * Cz, rec, RS_COL, sizeof(E), rows, fill);
+  };
+  auto row = [&](auto *&dst, size_t len) {
+    using E = std::remove_pointer_t<std::remove_reference_t<decltype(dst)>>;
+    dst = carve<E>(p, base, len * Cz, rec, RS_ROW, len * sizeof(E));
+  };
+  auto shared = [&](auto *&dst, size_t count) {
+    using E = std::remove_const_t<std::remove_pointer_t<std::remove_reference_t<decltype(dst)>>>;
+    dst = carve<E>(p, base, count, rec);
+  };
   S.C = C;
   S.mode = mode;
   S.dcd_tick = (mode == MODE_OQPSK && (flags & AERO_F_DCD_TICK)) ? 1 : 0;
   S.g = g;
-  S.ds = carve<double>(p, (size_t)DS_COUNT * C);
-  S.is = carve<int>(p, (size_t)IS_COUNT * C);
-  S.ls = carve<long long>(p, (size_t)LS_COUNT * C);
-  S.fir = carve<double>(p, (size_t)2 * g.ntaps * C);
-  S.agc = carve<double>(p, (size_t)g.agc_len * C);
-  S.dsm = carve<double2>(p, msk ? (size_t)g.dsm_len * C : 1);
-  S.d8 = carve<double>(p, msk ? (size_t)g.d8_len * C : 1);
-  S.marg = carve<double>(p, (size_t)g.marg_len * C);
-  S.dt = carve<double2>(p, (size_t)g.dt_len * C);
+  col(S.ds, DS_COUNT, RF_DS);
+  col(S.is, IS_COUNT, RF_IS);
+  col(S.ls, LS_COUNT);
+  col(S.fir, (size_t)2 * g.ntaps);
+  col(S.agc, (size_t)g.agc_len);
+  if (msk) {
+    col(S.dsm, (size_t)g.dsm_len);
+    col(S.d8, (size_t)g.d8_len);
+  } else {
+    shared(S.dsm, 1);
+    shared(S.d8, 1);
+  }
+  row(S.marg, (size_t)g.marg_len);
+  row(S.dt, (size_t)g.dt_len);
   // OQPSK: pm holds MSEcalc's (pm, ms) pairs, [C][ms_len] double2 (demod_oqpsk.hip); MSK: ms = msema
-  S.pm = carve<double>(p, msk ? 1 : (size_t)2 * g.ms_len * C);
-  S.ms = carve<double>(p, msk ? (size_t)g.ms_len * C : 1);
-  S.pcm = carve<int16_t>(p, (size_t)PCM_CAP * C);
+  if (msk) {
+    shared(S.pm, 1);
+    row(S.ms, (size_t)g.ms_len);
+  } else {
+    row(S.pm, (size_t)2 * g.ms_len);
+    shared(S.ms, 1);
+  }
+  col(S.pcm, (size_t)PCM_CAP);
   S.pcm_cap = PCM_CAP;
-  S.cring = carve<uint32_t>(p, (size_t)g.nfft * C);
-  S.y = carve<double>(p, (size_t)(g.y_hi - g.y_lo + 1) * C);
-  S.soft = carve<uint8_t>(p, (size_t)SOFT_RING * C);
+  row(S.cring, (size_t)g.nfft);
+  row(S.y, (size_t)(g.y_hi - g.y_lo + 1));
+  row(S.soft, (size_t)SOFT_RING);
   S.pt_cap = (flags & AERO_F_TRACE_PT) ? PT_CAP : 0;
-  S.pt = carve<double2>(p, (size_t)S.pt_cap * C);
+  row(S.pt, (size_t)S.pt_cap);
   S.hop_cap = HOP_CAP;
-  S.hops = carve<double>(p, (size_t)HOP_CAP * 6 * C);
-  S.hop_n = carve<int>(p, (size_t)C);
-  S.block = carve<uint8_t>(p, (size_t)2 * g.block * C);
-  S.overlap = carve<uint8_t>(p, (size_t)64 * C);
-  S.dl2 = carve<uint8_t>(p, (size_t)g.dl2_len * C);
-  S.jobs = carve<int>(p, (size_t)4 * C);
-  S.njobs = carve<int>(p, 1);
-  S.jobout = carve<uint8_t>(p, (size_t)JOB_OUT * C);
-  S.blocks_dbg = carve<uint8_t>(p, (flags & AERO_F_TRACE_BLOCKS) ? (size_t)2500 * C : 1);
+  row(S.hops, (size_t)HOP_CAP * 6);
+  row(S.hop_n, 1);
+  row(S.block, (size_t)2 * g.block);
+  row(S.overlap, 64);
+  row(S.dl2, (size_t)g.dl2_len);
+  shared(S.jobs, (size_t)4 * C);
+  shared(S.njobs, 1);
+  shared(S.jobout, (size_t)JOB_OUT * C);
+  if (flags & AERO_F_TRACE_BLOCKS)
+    row(S.blocks_dbg, 2500);
+  else
+    shared(S.blocks_dbg, 1);
   const bool cch = mode == MODE_C8400;
-  S.cin = carve<uint32_t>(p, cch ? (size_t)C_IN_RING * C : 1);
-  S.cout = carve<double2>(p, cch ? (size_t)C_OUT_RING * C : 1);
-  S.csig = carve<double2>(p, cch ? (size_t)C_FIR_SNZ * C : 1);
-  S.crem = carve<double2>(p, cch ? (size_t)(C_FIR_N - C_FIR_SNZ) * C : 1);
-  T.cker = carve<double2>(p, cch ? C_FIR_N : 1);
-  T.tw4 = carve<double2>(p, cch ? C_FIR_N : 1);
-  T.twi4 = carve<double2>(p, cch ? C_FIR_N : 1);
-  T.cwin = carve<double>(p, cch ? NFFT : 1);
-  T.cis = carve<double2>(p, WTSIZE);
-  T.tw = carve<double2>(p, g.nfft);
-  T.twi = carve<double2>(p, g.nfft);
-  T.twg = carve<double2>(p, g.nfft);
-  T.twgi = carve<double2>(p, g.nfft);
-  T.scr = carve<uint8_t>(p, 5000);
-  T.taps = carve<double>(p, MAX_TAPS);
+  if (cch) {
+    row(S.cin, (size_t)C_IN_RING);
+    row(S.cout, (size_t)C_OUT_RING);
+    row(S.csig, (size_t)C_FIR_SNZ);
+    row(S.crem, (size_t)(C_FIR_N - C_FIR_SNZ));
+  } else {
+    shared(S.cin, 1);
+    shared(S.cout, 1);
+    shared(S.csig, 1);
+    shared(S.crem, 1);
+  }
+  shared(T.cker, cch ? C_FIR_N : 1);
+  shared(T.tw4, cch ? C_FIR_N : 1);
+  shared(T.twi4, cch ? C_FIR_N : 1);
+  shared(T.cwin, cch ? NFFT : 1);
+  shared(T.cis, WTSIZE);
+  shared(T.tw, g.nfft);
+  shared(T.twi, g.nfft);
+  shared(T.twg, g.nfft);
+  shared(T.twgi, g.nfft);
+  shared(T.scr, 5000);
+  shared(T.taps, MAX_TAPS);
   return (size_t)(p - base);
 }
 
@@ -418,16 +474,14 @@ void ev_collect(Group *e) {
 // decode/mskdemodulator.cpp:7-218 (both as Decoder applies them); AeroL ctor
 // (decode/aerol.cpp:875-954).  Opened channels are initialised lazily, one
 // strided copy per field for the whole pending range.
-int init_scalars(Group *e, int lo, int hi) {
-  const int C = e->C, k = hi - lo;
-  std::vector<double> ds(DS_COUNT, 0.0);
-  std::vector<int> is(IS_COUNT, 0);
-  std::vector<long long> ls(LS_COUNT, 0);
-  if (e->mode == MODE_OQPSK) {
+void scalar_init(int mode, const ModeGeom &g, std::vector<double> &ds, std::vector<int> &is) {
+  ds.assign(DS_COUNT, 0.0);
+  is.assign(IS_COUNT, 0);
+  if (mode == MODE_OQPSK) {
     ds[DS_SO_FREQ] = 10500;
     ds[DS_SO_STEP] = (10500.0) * ((double)WTSIZE) / ((float)48000);
     ds[DS_MSE] = 100;
-  } else if (e->mode == MODE_C8400) {
+  } else if (mode == MODE_C8400) {
     // st_osc.SetFreq(fb = 8400, Fs) (oqpskdemodulator.cpp:225-227); the ctor's
     // mixer_fir_pre.SetFreq(freq_center = 8000, Fs) (:114), phase 0
     ds[DS_SO_FREQ] = 8400;
@@ -439,7 +493,7 @@ int init_scalars(Group *e, int lo, int hi) {
     // st_osc.SetFreq(fb / 2, Fs) (mskdemodulator.cpp:117); mse = 10.0 (:146);
     // DiffDecode::lastsoftstate = -1 (DSP.cpp:517-520)
     ds[DS_SO_FREQ] = 300;
-    ds[DS_SO_STEP] = (300.0) * ((double)WTSIZE) / ((float)e->g.fs);
+    ds[DS_SO_STEP] = (300.0) * ((double)WTSIZE) / ((float)g.fs);
     ds[DS_MSE] = 10.0;
     ds[DS_DIFF_LAST] = -1;
   }
@@ -447,6 +501,14 @@ int init_scalars(Group *e, int lo, int hi) {
   is[IS_COUNTDOWN] = 4;
   is[IS_EMPTYCD] = 1;
   is[IS_CNTR] = 1000000000;
+}
+
+int init_scalars(Group *e, int lo, int hi) {
+  const int C = e->C, k = hi - lo;
+  std::vector<double> ds;
+  std::vector<int> is;
+  std::vector<long long> ls(LS_COUNT, 0);
+  scalar_init(e->mode, e->g, ds, is);
   std::vector<double> vd(k);
   std::vector<int> vi(k);
   std::vector<long long> vl(k);
@@ -465,58 +527,73 @@ int init_scalars(Group *e, int lo, int hi) {
   return AERO_OK;
 }
 
-int flush_pending_init(Group *e) {
-  const int lo = e->init_lo, hi = e->nch;
-  if (lo >= hi) return AERO_OK;
-  if (int rc = init_scalars(e, lo, hi)) return rc;
-  e->init_lo = hi;
+// The slots closed channels left (aero_channel_close, msk_migrate) go back to
+// a new channel's state in one launch of the reset kernel (slot_reset.hip):
+// every per-channel array of layout() zeroed, as the zeroed pool leaves a
+// slot never used, and the scalar init.  Queued by the close, which drained
+// the group, and launched before the group's next push or run, so a batch of
+// closes costs one launch and no wait.
+int flush_pending_reset(Group *e) {
+  if (e->reset_pending.empty()) return AERO_OK;
+  // sorted, each slot once (one closed, reopened and closed again since the last launch is listed twice)
+  std::sort(e->reset_pending.begin(), e->reset_pending.end());
+  e->reset_pending.erase(std::unique(e->reset_pending.begin(), e->reset_pending.end()), e->reset_pending.end());
+  const int n = (int)e->reset_pending.size();
+  if (n > e->C) return AERO_E_INVALID;
+  if (!e->reset_ready) {  // first reuse in this group: the plan, the scalar init, the slot list
+    LayoutRec rec;
+    DevState S{};
+    DevTables T{};
+    layout(S, T, e->mode, e->g, e->C, e->flags, nullptr, &rec);
+    const std::vector<ResetSeg> plan = reset_plan(rec);
+    if (rec.bad || DS_COUNT > RESET_DS_MAX || IS_COUNT > RESET_IS_MAX) return AERO_E_INVALID;
+    std::vector<double> ds;
+    std::vector<int> is;
+    scalar_init(e->mode, e->g, ds, is);
+    ResetInit init{};
+    std::copy(ds.begin(), ds.end(), init.ds);
+    std::copy(is.begin(), is.end(), init.is);
+    // (a call that failed half way left what it had allocated: kept, the rest made now)
+    if (!e->d_reset_plan && hipMalloc(&e->d_reset_plan, sizeof(ResetSeg) * plan.size()) != hipSuccess)
+      return AERO_E_NOMEM;
+    if (!e->d_reset_init && hipMalloc(&e->d_reset_init, sizeof(ResetInit)) != hipSuccess) return AERO_E_NOMEM;
+    if (!e->d_reset_slots && hipMalloc(&e->d_reset_slots, sizeof(int) * 2 * e->C) != hipSuccess) return AERO_E_NOMEM;
+    if (!e->pin_reset_slots && hipHostMalloc(&e->pin_reset_slots, sizeof(int) * 2 * e->C) != hipSuccess)
+      return AERO_E_NOMEM;
+    HIPCHK(hipMemcpy(e->d_reset_plan, plan.data(), sizeof(ResetSeg) * plan.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_reset_init, &init, sizeof init, hipMemcpyHostToDevice));
+    if (!e->reset_ev) HIPCHK(hipEventCreateWithFlags(&e->reset_ev, hipEventDisableTiming));
+    e->reset_plan = plan;
+    e->reset_ready = true;  // only now: every buffer exists
+  }
+  HIPCHK(hipEventSynchronize(e->reset_ev));  // the last launch has read the list
+  for (int i = 0; i < n; i++) {
+    if (e->reset_pending[i] < 0 || e->reset_pending[i] >= e->C) return AERO_E_INVALID;
+    e->pin_reset_slots[i] = e->reset_pending[i];
+    e->pin_reset_slots[e->C + i] = 0;  // one scalar init per continuous group
+  }
+  HIPCHK(hipMemcpyAsync(e->d_reset_slots, e->pin_reset_slots, sizeof(int) * 2 * e->C, hipMemcpyHostToDevice, e->st));
+  launch_reset_slots(e->st, e->pool, e->d_reset_plan, (int)e->reset_plan.size(), e->d_reset_slots,
+                     e->d_reset_slots + e->C, n, e->d_reset_init, reset_items(e->reset_plan, n));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(e->reset_ev, e->st));
+  e->reset_done = true;
+  e->reset_launches++;
+  for (int c : e->reset_pending) e->reset_wait[c] = 0;
+  e->reset_pending.clear();
   return AERO_OK;
 }
 
-// A freed slot (free_slots) back to a new channel's state: every per-channel
-// row zeroed, as the zeroed pool leaves a slot never used, then the scalar
-// init.  The group is idle (its stream drained first).
-int reset_slot(Group *e, int c) {
-  const DevState &S = e->S;
-  const ModeGeom &g = e->g;
-  const size_t C = (size_t)e->C;
-  const bool msk = e->mode != MODE_OQPSK;
-  hipStream_t st = e->st;
-  HIPCHK(hipStreamSynchronize(st));
-  auto col = [&](void *base, size_t elem, size_t rows) {  // time-major [rows][C]: one element per row
-    return hipMemset2DAsync((char *)base + elem * c, elem * C, 0, elem, rows, st);
-  };
-  auto row = [&](void *base, size_t bytes) {  // channel-major [C][len]
-    return hipMemsetAsync((char *)base + bytes * c, 0, bytes, st);
-  };
-  HIPCHK(col(S.fir, 8, (size_t)2 * g.ntaps));
-  HIPCHK(col(S.agc, 8, (size_t)g.agc_len));
-  if (msk) {
-    HIPCHK(col(S.dsm, 16, (size_t)g.dsm_len));
-    HIPCHK(col(S.d8, 8, (size_t)g.d8_len));
-    HIPCHK(row(S.ms, (size_t)8 * g.ms_len));
-  } else {
-    HIPCHK(row(S.pm, (size_t)16 * g.ms_len));
+// before a group's push or run: the scalar init of the channels opened since
+// the last one, then the reset of the slots closed since (a slot both opened
+// and closed since gets the reset's state, which is the same)
+int flush_pending_init(Group *e) {
+  const int lo = e->init_lo, hi = e->nch;
+  if (lo < hi) {
+    if (int rc = init_scalars(e, lo, hi)) return rc;
+    e->init_lo = hi;
   }
-  HIPCHK(col(S.pcm, 2, (size_t)PCM_CAP));
-  HIPCHK(row(S.marg, (size_t)8 * g.marg_len));
-  HIPCHK(row(S.dt, (size_t)16 * g.dt_len));
-  HIPCHK(row(S.cring, (size_t)4 * g.nfft));
-  HIPCHK(row(S.y, (size_t)8 * (g.y_hi - g.y_lo + 1)));
-  HIPCHK(row(S.soft, (size_t)SOFT_RING));
-  if (S.pt_cap) HIPCHK(row(S.pt, (size_t)16 * S.pt_cap));
-  HIPCHK(row(S.hops, (size_t)8 * 6 * HOP_CAP));
-  HIPCHK(row(S.hop_n, 4));
-  HIPCHK(row(S.block, (size_t)2 * g.block));
-  HIPCHK(row(S.overlap, 64));
-  HIPCHK(row(S.dl2, (size_t)g.dl2_len));
-  if (e->flags & AERO_F_TRACE_BLOCKS) HIPCHK(row(S.blocks_dbg, 2500));
-  if (e->mode == MODE_C8400) {  // JFastFir's state: no outputs yet, no remainder
-    HIPCHK(row(S.csig, (size_t)16 * C_FIR_SNZ));
-    HIPCHK(row(S.crem, (size_t)16 * (C_FIR_N - C_FIR_SNZ)));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return init_scalars(e, c, c + 1);
+  return flush_pending_reset(e);
 }
 
 // CRC-16 of one SU (AeroLcrc16::calcusingbytes, decode/aerol.h:332-367) and the
@@ -701,11 +778,16 @@ int collect_traces(Group *e) {
   // the channels whose traces are kept (aero_trace_select), and whether
   // their rows are copied one by one (a few channels of a large group)
   std::vector<int> sel;
+  // (a slot holds its closed channel's counters until the reset kernel has
+  // run, whether it is still free or already reopened: nothing is collected
+  // for it, and the reopened channel has produced nothing yet)
+  auto live = [e](int c) { return e->gch[c] >= 0 && !e->reset_wait[c]; };
   if (!e->trace_some) {
-    sel.resize(nch);
-    for (int c = 0; c < nch; c++) sel[c] = c;
+    for (int c = 0; c < nch; c++)
+      if (live(c)) sel.push_back(c);
   } else {
-    sel = e->trace_list;
+    for (int c : e->trace_list)
+      if (live(c)) sel.push_back(c);
   }
   const bool rows = e->trace_some;
   std::vector<int> hn(nch);
@@ -1069,7 +1151,7 @@ int drain_group(Group *e) {
 
 // engine channel -> burst-group index (its group in *bg), or -1
 int route_burst(aero_engine *e, int ch, BurstGroup **bg = nullptr) {
-  if (!e || ch < 0 || ch >= (int)e->chmap.size()) return -1;
+  if (!e || ch < 0 || ch >= (int)e->chmap.size() || e->chmap[ch].first < 0) return -1;
   const int k = e->chmap[ch].first - MODE_BURST;
   if (k < 0 || k > 1) return -1;
   if (bg) *bg = e->burst[k];
@@ -1200,7 +1282,8 @@ int group_create(aero_engine *E, int mode, int gid, int fs, std::unique_ptr<Grou
   // its rate: a small pool (another group of the rate opens when it is
   // full), not max_channels (one 96 kHz channel of a 65536-channel engine
   // would otherwise ask for ~50 GB of AGC ring)
-  e->C = (E->max_channels + 63) & ~63;
+  // (aero_engine_reserve: the channels the host said this kind will hold)
+  e->C = (E->capacity(msk_generic(mode) ? mode : gid, msk_generic(mode) ? fs : 0) + 63) & ~63;
   if (msk_generic(mode)) e->C = std::min(e->C, GENERIC_GROUP_CAP);
   DevState S{};
   DevTables T{};
@@ -1387,6 +1470,11 @@ void group_destroy(Group *e) {
     if (e->d_cjobs[k]) (void)hipFree(e->d_cjobs[k]);
     if (e->cjob_ev[k]) (void)hipEventDestroy(e->cjob_ev[k]);
   }
+  if (e->d_reset_plan) (void)hipFree(e->d_reset_plan);
+  if (e->d_reset_init) (void)hipFree(e->d_reset_init);
+  if (e->d_reset_slots) (void)hipFree(e->d_reset_slots);
+  if (e->pin_reset_slots) (void)hipHostFree(e->pin_reset_slots);
+  if (e->reset_ev) (void)hipEventDestroy(e->reset_ev);
   if (e->pin_stat) (void)hipHostFree(e->pin_stat);
   if (e->pin_pcm) (void)hipHostFree(e->pin_pcm);
   if (e->pin_pcm_ev) (void)hipEventDestroy(e->pin_pcm_ev);
@@ -1408,7 +1496,8 @@ namespace {
 
 // engine channel -> (group, local index); nullptr if out of range
 Group *route(aero_engine *e, int ch, int &local) {
-  if (!e || ch < 0 || ch >= (int)e->chmap.size() || e->chmap[ch].first >= MODE_BURST) return nullptr;
+  if (!e || ch < 0 || ch >= (int)e->chmap.size() || e->chmap[ch].first >= MODE_BURST || e->chmap[ch].first < 0)
+    return nullptr;  // out of range, burst, or closed
   local = e->chmap[ch].second;
   return e->groups[e->chmap[ch].first].get();
 }
@@ -1529,6 +1618,8 @@ int push_common(Group *e, const int16_t *src, size_t n, size_t ld, int nch, int 
       HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
       HIPCHK(hipStreamCreateWithPriority(&e->st_in, hipStreamNonBlocking, hi));
     }
+    // a reused slot's ring rows are zeroed on the main stream first
+    if (e->reset_done) HIPCHK(hipStreamWaitEvent(e->st_in, e->reset_ev, 0));
     // rows of samples [start, start + n) overwrite those of samples below
     // start + n - PCM_CAP: wait for the demod launch that consumed them
     const long long need = start + (long long)n - PCM_CAP;
@@ -1687,23 +1778,15 @@ int group_add_channel(aero_engine *e, int gid, const aero_channel_cfg &cfg, int 
   if (!e->groups[gid])
     if (int rc = group_create(e, gid, gid, 0, e->groups[gid])) return rc;
   Group *g = e->groups[gid].get();
-  if (!g->free_slots.empty()) {  // a slot an MSK channel moved out of
-    if (int rc = flush_pending_init(g)) return rc;
-    const int c = g->free_slots.back();
-    if (int rc = reset_slot(g, c)) return rc;
-    g->free_slots.pop_back();
+  if (!g->free_slots.empty()) {
+    // the smallest slot a closed or moved channel left: release_slot reset its
+    // host state and queued its device state for the reset kernel
+    const auto it = std::min_element(g->free_slots.begin(), g->free_slots.end());
+    const int c = *it;
+    g->free_slots.erase(it);
     g->cfg[c] = cfg;
     g->gch[c] = gc;
-    g->avail[c] = g->nsamp[c] = g->hops[c] = 0;
     g->host[c].reset(new PChannelHost(cfg.disable_reassembly != 0));
-    g->infofield[c].clear();
-    g->soft_hold[c].clear();
-    g->hop_hold[c].clear();
-    g->pt_hold[c].clear();
-    g->blk_hold[c].clear();
-    g->frame_hold[c].clear();
-    g->soft_seen[c] = 0;
-    g->hop_base[c] = 0;
     *local = c;
     return AERO_OK;
   }
@@ -1723,6 +1806,7 @@ int group_add_channel(aero_engine *e, int gid, const aero_channel_cfg &cfg, int 
   g->blk_hold.emplace_back();
   g->frame_hold.emplace_back();
   g->soft_seen.push_back(0);
+  g->reset_wait.push_back(0);
   g->hop_base.push_back(0);
   g->msg_end.emplace_back();
   g->pre_end.push_back(0);
@@ -1734,6 +1818,52 @@ int group_add_channel(aero_engine *e, int gid, const aero_channel_cfg &cfg, int 
   if (g->trace_some) g->trace_mask.resize(g->C, 0);
   *local = c;
   return AERO_OK;
+}
+
+// Local slot c of group gid, whose channel has left (aero_channel_close, or
+// msk_migrate with the channel's state moved out), back to a new channel's
+// state.  The caller drained the group (no queued GPU pass, no host frame
+// work), so nothing reads the slot until the group's next push or run, which
+// launches the reset kernel for every slot queued here first.  The host
+// mirrors are reset now; whatever the channel had pushed and not consumed, or
+// produced and not popped, is gone.
+void release_slot(aero_engine *e, int gid, int c) {
+  Group *g = e->groups[gid].get();
+  g->gch[c] = -1;
+  g->free_slots.push_back(c);
+  g->reset_pending.push_back(c);
+  g->reset_wait[c] = 1;
+  g->hq.erase(std::remove_if(g->hq.begin(), g->hq.end(), [c](const Group::HqItem &it) { return it.c == c; }),
+              g->hq.end());
+  if (g->hq.empty()) g->hq_used = 0;  // only its messages were queued: the staging is free again
+  g->avail[c] = g->nsamp[c] = g->hops[c] = 0;
+  g->host[c].reset(new PChannelHost(false));
+  g->infofield[c].clear();
+  g->soft_hold[c].clear();
+  g->hop_hold[c].clear();
+  g->pt_hold[c].clear();
+  g->blk_hold[c].clear();
+  g->frame_hold[c].clear();
+  g->soft_seen[c] = 0;
+  g->hop_base[c] = 0;
+  g->msg_end[c].clear();
+  g->pre_end[c] = 0;
+  g->cunit_hold[c].clear();
+  g->voice_hold[c].clear();
+  g->c_cd[c] = g->c_dcd[c] = g->c_edges[c] = 0;
+  if (g->trace_some && g->trace_mask[c]) {
+    g->trace_mask[c] = 0;
+    g->trace_list.erase(std::remove(g->trace_list.begin(), g->trace_list.end(), c), g->trace_list.end());
+  }
+  // a generic-rate group nobody is left in is released (its device pool,
+  // stream and pinned buffers); its counters stay in the engine's totals
+  if (msk_generic(g->mode) && (int)g->free_slots.size() == g->nch) {
+    e->retired_jobs += g->st_jobs.load();
+    e->retired_frames += g->st_frames.load();
+    e->retired_su_ok += g->st_su_ok.load();
+    e->retired_resets += g->reset_launches;
+    e->groups[gid].reset();
+  }
 }
 
 // MskDemodulator::dataReceived at another sample rate (decode/mskdemodulator.cpp
@@ -1768,6 +1898,10 @@ int msk_migrate(aero_engine *e, int ch, uint32_t fs) {
   if (int rc = group_add_channel(e, to, cfg, ch, &c2)) return rc;
   Group *h = e->groups[to].get();
   if (int rc = flush_pending_init(h)) return rc;
+  // c2 may be a freed slot whose reset has only just been launched (or is
+  // still queued behind the group's passes) on h's stream; the copies below
+  // are not ordered after that stream, so the reset finishes first
+  if (h->reset_done) HIPCHK(hipEventSynchronize(h->reset_ev));
   const int C = g->C, C2 = h->C;
   // scalar state: read the old channel's fields, apply setSettings, write
   std::vector<double> ds(DS_COUNT);
@@ -1847,16 +1981,7 @@ int msk_migrate(aero_engine *e, int ch, uint32_t fs) {
   e->chmap[ch] = {to, c2};
   // the old slot is free for the next channel of that group (it has no
   // samples left: the group ran and drained it above)
-  g->gch[c] = -1;
-  g->free_slots.push_back(c);
-  // a generic-rate group nobody is left in is released (its device pool,
-  // stream and pinned buffers); its counters stay in the engine's totals
-  if (msk_generic(g->mode) && (int)g->free_slots.size() == g->nch) {
-    e->retired_jobs += g->st_jobs.load();
-    e->retired_frames += g->st_frames.load();
-    e->retired_su_ok += g->st_su_ok.load();
-    e->groups[from].reset();
-  }
+  release_slot(e, from, c);
   return AERO_OK;
 }
 
@@ -1869,6 +1994,62 @@ Group *route_rate(aero_engine *e, int ch, uint32_t fs, int &local, int &rc) {
     return g;  // OQPSK only logs it (:626-628)
   if ((rc = msk_migrate(e, ch, fs))) return nullptr;
   return route(e, ch, local);
+}
+
+// the id aero_channel_open gives out next: the smallest closed one, else a new one
+int next_id(const aero_engine *e) { return e->free_ids.empty() ? (int)e->chmap.size() : *e->free_ids.begin(); }
+
+int take_id(aero_engine *e, int kind, int local) {
+  const int id = next_id(e);
+  if (id == (int)e->chmap.size()) {
+    e->chmap.push_back({kind, local});
+  } else {
+    e->free_ids.erase(e->free_ids.begin());
+    e->chmap[id] = {kind, local};
+  }
+  return id;
+}
+
+// The channel kinds (aero_channel_open, aero_engine_reserve) and the group
+// each maps to: *key is the gid of a fixed kind, MODE_BURST + BurstKind, or
+// the Mode of a generic-rate MSK group (then *gfs is its rate, else 0).
+// AERO_E_INVALID for a bit rate or OQPSK rate nothing serves, AERO_E_RATE for
+// an MSK rate outside what the kernels serve.
+int kind_key(const aero_channel_cfg *cfg, int *key, int *gfs) {
+  *gfs = 0;
+  if (cfg->burst) {
+    // aero-decode --burst: 10500 bps OQPSK at 48 kHz; 600 / 1200 bps MSK run
+    // one fb = 1200 demodulator configured for 48 kHz whatever rate the audio
+    // is labelled with (decode/decode.cpp:123-132; a mismatch is only logged,
+    // burstmskdemodulator.cpp:708-714)
+    if (cfg->bitrate == 10500 && cfg->fs == 48000)
+      *key = MODE_BURST + BURST_OQPSK;
+    else if ((cfg->bitrate == 600 || cfg->bitrate == 1200) && cfg->fs > 0)
+      *key = MODE_BURST + BURST_MSK;
+    else
+      return AERO_E_INVALID;
+    return AERO_OK;
+  }
+  // decode/decode.h:42 validBitRates: 10500 (48 kHz), 600 and 1200 at any
+  // rate MSK is served at (12 / 24 kHz as decode/decode.cpp:145); and the C
+  // channel, 8400 at 48 kHz (OqpskDemodulator at fb = 8400 + AeroL::DecodeC)
+  const bool oq = (cfg->bitrate == 10500 || cfg->bitrate == 8400) && cfg->fs == 48000;
+  if (!oq && !(cfg->bitrate == 600 || cfg->bitrate == 1200)) return AERO_E_INVALID;
+  if (!oq && (cfg->fs < (uint32_t)MSK_FS_MIN || cfg->fs > (uint32_t)MSK_FS_MAX)) return AERO_E_RATE;
+  if (oq) {
+    *key = cfg->bitrate == 8400 ? GID_C8400 : MODE_OQPSK;
+    return AERO_OK;
+  }
+  const int m = msk_mode((int)cfg->bitrate, (int)cfg->fs);
+  if (m >= 0) {
+    *key = m;
+    return AERO_OK;
+  }
+  MskGen mg;
+  if (!msk_gen_consts((int)cfg->fs, mg)) return AERO_E_RATE;  // as group_create reports it
+  *key = cfg->bitrate == 600 ? MODE_MSKG600 : MODE_MSKG1200;
+  *gfs = (int)cfg->fs;
+  return AERO_OK;
 }
 
 }  // namespace
@@ -1927,49 +2108,69 @@ void aero_engine_destroy(aero_engine *e) {
 
 int aero_channel_open(aero_engine *e, const aero_channel_cfg *cfg, int *ch_out) {
   if (!e || !cfg || !ch_out) return AERO_E_INVALID;
-  if (cfg->burst) {
-    // aero-decode --burst: 10500 bps OQPSK at 48 kHz; 600 / 1200 bps MSK run
-    // one fb = 1200 demodulator configured for 48 kHz whatever rate the audio
-    // is labelled with (decode/decode.cpp:123-132; a mismatch is only logged,
-    // burstmskdemodulator.cpp:708-714)
-    int kind;
-    if (cfg->bitrate == 10500 && cfg->fs == 48000)
-      kind = BURST_OQPSK;
-    else if ((cfg->bitrate == 600 || cfg->bitrate == 1200) && cfg->fs > 0)
-      kind = BURST_MSK;
-    else
-      return AERO_E_INVALID;
+  int key, gfs;
+  if (int rc = kind_key(cfg, &key, &gfs)) return rc;
+  if (key >= MODE_BURST) {
+    const int kind = key - MODE_BURST;
     HIPCHK(hipSetDevice(e->device));
     if (!e->burst[kind]) {
-      if (int rc = burst_group_create(e->device, e->flags, e->max_channels, kind, &e->burst[kind])) return rc;
+      if (int rc = burst_group_create(e->device, e->flags, e->capacity(key, 0), kind, &e->burst[kind])) return rc;
       burst_group_set_pool(e->burst[kind], e->hpool.get());
     }
     int local;
     if (int rc = burst_open(e->burst[kind], (int)cfg->bitrate, cfg->disable_reassembly != 0, &local)) return rc;
-    *ch_out = (int)e->chmap.size();
-    e->chmap.push_back({MODE_BURST + kind, local});
+    *ch_out = take_id(e, key, local);
     return AERO_OK;
   }
-  // decode/decode.h:42 validBitRates: 10500 (48 kHz), 600 and 1200 at any
-  // rate MSK is served at (12 / 24 kHz as decode/decode.cpp:145); and the C
-  // channel, 8400 at 48 kHz (OqpskDemodulator at fb = 8400 + AeroL::DecodeC)
-  const bool oq = (cfg->bitrate == 10500 || cfg->bitrate == 8400) && cfg->fs == 48000;
-  if (!oq && !(cfg->bitrate == 600 || cfg->bitrate == 1200)) return AERO_E_INVALID;
-  if (!oq && (cfg->fs < (uint32_t)MSK_FS_MIN || cfg->fs > (uint32_t)MSK_FS_MAX)) return AERO_E_RATE;
   HIPCHK(hipSetDevice(e->device));
   host_wait(e);  // the host task indexes the per-channel tables
-  int gid = MODE_OQPSK;
-  if (cfg->bitrate == 8400) {
-    gid = GID_C8400;
+  int gid = key;  // a fixed kind's group id; a generic-rate group is found or created
+  if (key == GID_C8400) {
     if (!e->groups[gid])
       if (int rc = group_create(e, MODE_C8400, gid, 48000, e->groups[gid])) return rc;
-  } else if (cfg->bitrate != 10500) {
+  } else if (gfs) {
     if (int rc = msk_gid(e, (int)cfg->bitrate, (int)cfg->fs, gid)) return rc;
   }
   int c;
-  if (int rc = group_add_channel(e, gid, *cfg, (int)e->chmap.size(), &c)) return rc;
-  *ch_out = (int)e->chmap.size();
-  e->chmap.push_back({gid, c});
+  if (int rc = group_add_channel(e, gid, *cfg, next_id(e), &c)) return rc;
+  *ch_out = take_id(e, gid, c);
+  return AERO_OK;
+}
+
+int aero_channel_close(aero_engine *e, int ch) {
+  if (!e || ch < 0 || ch >= (int)e->chmap.size() || e->chmap[ch].first < 0) return AERO_E_INVALID;
+  HIPCHK(hipSetDevice(e->device));
+  const int kind = e->chmap[ch].first, c = e->chmap[ch].second;
+  if (kind >= MODE_BURST) {
+    if (int rc = burst_close(e->burst[kind - MODE_BURST], c)) return rc;
+  } else {
+    // the group's queued passes and the host frame work finish first (they
+    // index the slot); no pass is run for the samples still pending
+    // (nothing is launched here: the slot joins the group's reset list, and
+    // the list goes to the reset kernel in one launch at the next push or run)
+    Group *g = e->groups[kind].get();
+    if (int rc = drain_group(g)) return rc;
+    host_wait(e);
+    release_slot(e, kind, c);
+  }
+  e->chmap[ch] = {-1, -1};
+  e->free_ids.insert(ch);
+  return AERO_OK;
+}
+
+int aero_engine_reserve(aero_engine *e, const aero_channel_cfg *kind, int n) {
+  if (!e || !kind || n < 1 || n > e->max_channels) return AERO_E_INVALID;
+  int key, gfs;
+  if (kind_key(kind, &key, &gfs)) return AERO_E_INVALID;
+  if (key >= MODE_BURST) {
+    if (e->burst[key - MODE_BURST]) return AERO_E_INVALID;
+  } else if (gfs) {
+    for (size_t k = MODE_COUNT + 1; k < e->groups.size(); k++)
+      if (e->groups[k] && e->groups[k]->mode == key && e->groups[k]->g.fs == gfs) return AERO_E_INVALID;
+  } else if (e->groups[key]) {
+    return AERO_E_INVALID;
+  }
+  e->reserved[{key, gfs}] = n;
   return AERO_OK;
 }
 
@@ -2041,6 +2242,7 @@ int aero_push_pcm_batch(aero_engine *e, const int16_t *pcm, size_t n, size_t ld,
   if (!e || !pcm || nch <= 0 || nch > (int)e->chmap.size() || ld < (size_t)nch) return AERO_E_INVALID;
   // channels [0, nch) must be one kind, opened in order (local == engine index)
   const int mode = e->chmap[0].first;
+  if (mode < 0) return AERO_E_INVALID;  // channel 0 is closed
   for (int j = 0; j < nch; j++)
     if (e->chmap[j].first != mode || e->chmap[j].second != j) return AERO_E_INVALID;
   if (mode >= MODE_BURST) {  // one message of n <= 16384 samples per channel
@@ -2123,6 +2325,7 @@ int aero_pop_items_all(aero_engine *e, aero_acars_item *dst, int *ch, size_t cap
   host_wait(e);
   size_t k = 0;
   for (int gc = 0; gc < (int)e->chmap.size() && k < cap; gc++) {
+    if (e->chmap[gc].first < 0) continue;  // closed
     auto &v = e->chmap[gc].first >= MODE_BURST
                   ? burst_items(e->burst[e->chmap[gc].first - MODE_BURST], e->chmap[gc].second)
                   : e->groups[e->chmap[gc].first]->host[e->chmap[gc].second]->items;
@@ -2264,8 +2467,15 @@ int aero_stat(aero_engine *e, const char *name, uint64_t *value) {
   uint64_t v = 0;
   const std::string n(name);
   if (n != "rt_tests" && n != "rt_packets" && n != "rt_pass_max" && n != "viterbi_jobs" && n != "frames" &&
-      n != "su_crc_ok" && n != "device_bytes" && n != "groups")
+      n != "su_crc_ok" && n != "device_bytes" && n != "groups" && n != "slot_resets")
     return AERO_E_INVALID;
+  if (n == "slot_resets") {  // launches of the reset kernel (one per batch of closed slots and group)
+    v = e->retired_resets + burst_stat(e->burst[0], 3) + burst_stat(e->burst[1], 3);
+    for (auto &g : e->groups)
+      if (g) v += g->reset_launches;
+    *value = v;
+    return AERO_OK;
+  }
   if (n == "device_bytes" || n == "groups") {  // continuous groups' device pools, and how many exist
     for (auto &g : e->groups)
       if (g) v += n == "groups" ? 1 : (uint64_t)g->pool_bytes;
@@ -2404,6 +2614,8 @@ int aero_device_math(aero_engine *e, int fn, const double *x, const double *y, d
 int aero_engine_feed_dev(aero_engine *e, int nitems, const int *ch, const int16_t *const *src, const size_t *n,
                          const uint32_t *fs, hipEvent_t ready, hipStream_t producer) {
   if (!e || nitems < 0 || (nitems && (!ch || !src || !n || !fs))) return AERO_E_INVALID;
+  for (int i = 0; i < nitems; i++)  // a closed channel: nothing of the call is fed
+    if (ch[i] >= 0 && ch[i] < (int)e->chmap.size() && e->chmap[ch[i]].first < 0) return AERO_E_INVALID;
   HIPCHK(hipSetDevice(e->device));
   // per group (gid; a rate change below may add a generic-rate group)
   std::vector<std::vector<std::pair<int, std::pair<const int16_t *, size_t>>>> per(e->groups.size());
@@ -2456,6 +2668,57 @@ extern "C" void aero_x_coarse_stamps(unsigned long long *out12) { coarse_read_st
 extern "C" void aero_x_viterbi_stamps(unsigned long long *out4) { viterbi_read_stamps(out4); }
 // the burst OQPSK demod's per-section cycle totals (AERO_X_BSTAMPS build; burst.hip)
 extern "C" void aero_x_burst_stamps(unsigned long long *out16) { burst_read_stamps(out16); }
+
+// host check (tests/test_channel_lifecycle_host.py; no GPU): the reset plan
+// of slot `slot` in a pool of C channels, as the reset kernel addresses it.
+// kind: a Mode (MODE_C8400 included), a generic-rate MSK Mode | fs << 8, or
+// 100 + BurstKind.  Records of 7 uint64: byte offset of the slot's first
+// row, bytes per row, rows, row pitch, ResetKind, ResetFill, bytes of the
+// whole array.  slot -1: every array of the layout instead (offset of the
+// array; ResetKind 0 for what belongs to no slot), then one record of
+// ResetKind 3 whose offset is the pool size.  Returns the record count (at
+// most `cap` are written) or a negative AERO_E_*.
+extern "C" int aero_x_reset_plan(int kind, int C, int flags, int slot, uint64_t *out, int cap) {
+  if (C < 64 || C % 64 || slot < -1 || slot >= C || (cap && !out)) return AERO_E_INVALID;
+  LayoutRec rec;
+  size_t pool = 0;
+  if (kind == 100 || kind == 101) {
+    pool = burst_layout_plan(kind - 100, C, &rec);
+  } else {
+    const int mode = kind & 0xFF, fs = kind >> 8;
+    ModeGeom g;
+    if (msk_generic(mode)) {
+      MskGen mg;
+      if (!msk_gen_consts(fs, mg)) return AERO_E_RATE;
+      g = msk_geom(msk_bitrate(mode), fs);
+    } else if ((mode >= 0 && mode < MODE_COUNT && !fs) || (mode == MODE_C8400 && !fs)) {
+      g = mode_geom(mode);
+    } else {
+      return AERO_E_INVALID;
+    }
+    DevState S{};
+    DevTables T{};
+    pool = layout(S, T, mode, g, C, flags, nullptr, &rec);
+  }
+  if (rec.bad) return AERO_E_INVALID;
+  std::vector<ResetSeg> segs = slot < 0 ? rec.segs : reset_plan(rec);
+  if (slot < 0) {
+    ResetSeg end{};
+    end.off = pool;
+    end.kind = 3;
+    segs.push_back(end);
+  }
+  int k = 0;
+  for (const ResetSeg &s : segs) {
+    if (k < cap) {
+      const uint64_t r[7] = {s.off + (slot < 0 ? 0 : (uint64_t)slot * s.elem), s.elem, s.rows, s.pitch,
+                             (uint64_t)s.kind, (uint64_t)s.fill, s.bytes};
+      memcpy(out + (size_t)7 * k, r, sizeof r);
+    }
+    k++;
+  }
+  return k;
+}
 
 // host check (tests/test_abi.py): the constants a generic-rate MSK group
 // would run with at sample rate fs (msk_gen_consts); iout: sps, d8_old,

@@ -469,6 +469,14 @@ int main(int argc, char **argv) {
           AH_WARN("Please confirm and verify that the specified topic is correct and that aero-publish is using "
                   "correct settings%s", tag(t).c_str());
           t.live = false;  // a reference process per topic: this one exits
+          if (multi) {
+            // the topic's channel is closed: no more pushes, polls or items for
+            // it, and its id and slot are free for another open (the slot stays
+            // in the group's launches as an idle channel).  What it has decoded
+            // so far is printed first: the close drops what is not popped
+            if (aero_sync(eng) == AERO_OK) drain();
+            aero_channel_close(eng, t.ch);
+          }
         }
       }
       any_live |= t.live;

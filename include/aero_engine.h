@@ -97,6 +97,40 @@ void aero_engine_destroy(aero_engine *e);
  * for an MSK rate outside that range. */
 int aero_channel_open(aero_engine *e, const aero_channel_cfg *cfg, int *ch_out);
 
+/* Closes one channel: ~Decoder for one topic (decode/decode.cpp:243-260).
+ * The channel's group finishes its queued GPU passes and host frame work
+ * first.  Samples pushed to ch and not yet consumed by a run are dropped, and
+ * so is every output not yet popped (items, also those waiting in
+ * aero_pop_items_all, soft bits, hops, pt, blocks, frames, R/T tests and
+ * packets, C units, voice): a host that wants the channel's tail calls
+ * aero_flush and pops before it closes.  Other channels' outputs do not
+ * change by one bit, wherever the close falls between their runs.
+ *
+ * Until the id is given out again, every call that takes ch returns
+ * AERO_E_INVALID (a second close too, and aero_trace_select or
+ * aero_chan_feed with ch in their lists, which then do nothing).
+ * aero_channel_open returns the smallest free id, and takes the smallest
+ * free slot of the kind's group; the reopened channel starts as the first
+ * channel of a new engine does (hop indices, DCD edges and event counters
+ * count from its first sample).  The slot's device state is reset by one
+ * kernel launch for every slot closed since the group last ran, at the
+ * group's next push or run (or per-channel query: aero_channel_stat and
+ * aero_channel_get_events read device state).  A generic-rate MSK group is
+ * released when its last channel leaves. */
+int aero_channel_close(aero_engine *e, int ch);
+
+/* Declares that the engine will hold at most n channels of `kind`
+ * (bitrate / burst / fs as for aero_channel_open) at once: the kind's group
+ * is then created with n slots (rounded up to 64, as max_channels is)
+ * instead of max_channels, and the n + 1st open returns AERO_E_FULL until a
+ * channel of the kind is closed.  For kinds a large engine holds few of:
+ * one C channel costs 2.4 MB of rings per slot of its group.
+ * AERO_E_INVALID when the kind's group already exists, n < 1,
+ * n > max_channels, or the kind is one aero_channel_open refuses.  A
+ * generic-rate MSK group holds at most 256 channels whatever is reserved.
+ * Without this call a group has max_channels slots. */
+int aero_engine_reserve(aero_engine *e, const aero_channel_cfg *kind, int n);
+
 /* One ZMQ message == one call: Decoder::audioReceived ->
  * OqpskDemodulator::dataReceived / MskDemodulator::dataReceived
  * (decode/decode.cpp:352, decode/oqpskdemodulator.cpp:624-630,
@@ -118,7 +152,11 @@ int aero_push_pcm(aero_engine *e, int ch, const int16_t *pcm, size_t n, uint32_t
  * decode/burstoqpskdemodulator.cpp:264).  The channels must have been opened
  * in order into one group (engine channel j is the group's slot j): once an
  * MSK rate change has moved a channel into a slot another channel left, that
- * group no longer qualifies (AERO_E_INVALID; push per channel instead). */
+ * group no longer qualifies (AERO_E_INVALID; push per channel instead).
+ * Closing and reopening channels of an engine of one kind keeps the
+ * condition: the smallest free id gets the smallest free slot (the reopened
+ * channels restart at sample 0, so a continuous batch is lockstep again only
+ * once every channel of it has been reopened). */
 int aero_push_pcm_batch(aero_engine *e, const int16_t *pcm, size_t n, size_t ld, int nch, int dev);
 
 /* aero_push_pcm with pcm a HIP device pointer (e.g. channeliser audio already
@@ -200,7 +238,9 @@ void aero_timing_reset(aero_engine *e);
  * channels: "rt_tests" (RTChannelDeleaveFECScram decodes run),
  * "rt_packets" (R/T packets that passed their CRCs), "rt_pass_max" (the most
  * R/T tests one pass handed to the host; from 256 on they are split over the
- * host threads).  Joins the
+ * host threads); "slot_resets": launches of the kernel that resets closed
+ * channels' slots (one per group for all the slots closed since the group
+ * last pushed or ran).  Joins the
  * asynchronous host frame work first.  AERO_E_INVALID for another name. */
 int aero_stat(aero_engine *e, const char *name, uint64_t *value);
 
