@@ -92,6 +92,11 @@ _SIGS = {
     'aero_channel_open': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ChannelCfg), ctypes.POINTER(ctypes.c_int)]),
     'aero_channel_close': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'aero_engine_reserve': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ChannelCfg), ctypes.c_int]),
+    'aero_channel_export': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    'aero_channel_import': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_int)]),
     'aero_push_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                      ctypes.c_uint32]),
     'aero_push_pcm_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
@@ -234,6 +239,21 @@ def item_line(it):
     return head + ' label=' + hx(label) + ' reg=' + hx(reg) + ' msg=' + hx(msg)
 
 
+def blob_kinds(blob):
+    """(bitrate, burst, fs, disable_reassembly) of every blob of an exported
+    batch (the header fields of include/aero_engine.h; lengths checked)."""
+    import struct
+    out, pos = [], 0
+    while pos + 48 <= len(blob):
+        bitrate, burst, fs, dis = struct.unpack_from('<iiIi', blob, pos + 12)
+        total, = struct.unpack_from('<Q', blob, pos + 40)
+        if total < 64 or pos + total > len(blob):
+            break
+        out.append((bitrate, burst, fs, dis))
+        pos += total
+    return out
+
+
 class Engine:
     """Batched MI355X Aero demodulator (one engine per GPU)."""
 
@@ -279,6 +299,46 @@ class Engine:
         undelivered outputs; its id and slot go to the next open_channel."""
         _check(self.lib.aero_channel_close(self.h, ch), 'aero_channel_close')
         self._fs.pop(ch, None)
+
+    def export_channels(self, chans):
+        """aero_channel_export: a snapshot of the channels' decoder state, one
+        blob per channel back to back; the channels stay open."""
+        chans = list(chans)
+        arr = (ctypes.c_int * max(1, len(chans)))(*chans)
+        need = ctypes.c_size_t()
+        _check(self.lib.aero_channel_export(self.h, arr, len(chans), None, 0, ctypes.byref(need)),
+               'aero_channel_export')
+        buf = np.empty(max(1, need.value), dtype=np.uint8)
+        _check(self.lib.aero_channel_export(self.h, arr, len(chans), buf.ctypes.data, need.value,
+                                            ctypes.byref(need)), 'aero_channel_export')
+        return buf[:need.value].tobytes()
+
+    def export_channel(self, ch):
+        return self.export_channels([ch])
+
+    def import_channels(self, blob):
+        """aero_channel_import: opens one channel per blob with the exported
+        state; returns their ids (all of the batch or, on an error, none)."""
+        src = np.frombuffer(blob, dtype=np.uint8)
+        # a blob is at least its 64 bytes of header and section lengths
+        cap = max(1, len(src) // 64)
+        out = (ctypes.c_int * cap)()
+        n = ctypes.c_int()
+        _check(self.lib.aero_channel_import(self.h, src.ctypes.data if len(src) else None, len(src), out, cap,
+                                            ctypes.byref(n)), 'aero_channel_import')
+        chans = [out[i] for i in range(n.value)]
+        kinds = blob_kinds(blob)
+        for ch, (bitrate, burst, fs, dis) in zip(chans, kinds):
+            self._fs[ch] = fs
+        return chans
+
+    def import_channel(self, blob):
+        chans = self.import_channels(blob)
+        if len(chans) != 1:
+            for ch in chans:
+                self.close_channel(ch)
+            raise ValueError('import_channel: %d blobs' % len(chans))
+        return chans[0]
 
     def reserve(self, n, bitrate=10500, fs=None, burst=False):
         """aero_engine_reserve: the kind's group is created with n slots
@@ -421,7 +481,8 @@ class Engine:
 
     def stat(self, name):
         """aero_stat counter: 'viterbi_jobs', 'frames', 'su_crc_ok' (and burst 'rt_*'), or the
-        continuous groups' 'device_bytes' / 'groups', or 'slot_resets' (reset-kernel launches)."""
+        continuous groups' 'device_bytes' / 'groups', 'slot_resets' (reset-kernel launches) or
+        'slot_copies' (pack / unpack launches of export_channels / import_channels)."""
         v = ctypes.c_uint64()
         _check(self.lib.aero_stat(self.h, name.encode(), ctypes.byref(v)), 'aero_stat')
         return int(v.value)

@@ -30,8 +30,8 @@ HIP_FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH] + FP
 CXX_FLAGS = ['-O2', '-std=c++17', '-fPIC', '-Wall'] + FP
 
 HIP_SRCS = ['demod_oqpsk.hip', 'demod_msk.hip', 'coarse.hip', 'aerol.hip', 'engine.hip', 'chan.hip', 'burst.hip', 'burst_msk.hip',
-            'burst_engine.hip', 'cchan.hip', 'slot_reset.hip']
-CXX_SRCS = ['tables_host.cpp', 'acars_host.cpp']
+            'burst_engine.hip', 'cchan.hip', 'slot_reset.hip', 'slot_copy.hip']
+CXX_SRCS = ['tables_host.cpp', 'acars_host.cpp', 'chan_blob.cpp']
 # Per-file codegen: the burst demodulators' loops hold their state in
 # registers; LLVM's machine LICM hoists every FP64 constant of the inlined
 # libm ports out of the loop into SGPRs, hundreds of them, which then spill
@@ -125,12 +125,12 @@ def build_mathhost():
 
 HOSTCHECK_SO = os.path.join(ROOT, 'tools', 'libaero_hostcheck.so')
 HOSTCHECK_SRCS = [os.path.join(ROOT, 'tools', 'hostcheck.cpp'), os.path.join(CSRC, 'acars_host.cpp'),
-                  os.path.join(CSRC, 'tables_host.cpp')]
+                  os.path.join(CSRC, 'chan_blob.cpp'), os.path.join(CSRC, 'tables_host.cpp')]
 
 
 def build_hostcheck(out=HOSTCHECK_SO, extra=()):
     """Test-only CPU harness over the engine's host C++ (acars_host, tables_host)."""
-    deps = HOSTCHECK_SRCS + [os.path.join(CSRC, h) for h in ('acars_host.h', 'tables_host.h')]
+    deps = HOSTCHECK_SRCS + [os.path.join(CSRC, h) for h in ('acars_host.h', 'chan_blob.h', 'tables_host.h')]
     if _stale(out, deps):
         _run(['g++'] + CXX_FLAGS + list(extra) + ['-shared', '-o', out] + HOSTCHECK_SRCS + ['-lm'])
     return out

@@ -8,6 +8,7 @@
  * C-channel-assignment items (aerol.cpp:2099-2143).
  */
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -41,6 +42,12 @@ class PChannelHost {
   // marked downlink (parser.downlink = burstmode)
   void rt_packet(bool r_packet, const uint8_t *info, int len, int nsus);
   std::vector<aero_acars_item> items;
+  // The reassembly state (every member below; `items` is an output and does
+  // not travel) as bytes, appended to `out`, and back (chan_blob.cpp).  load
+  // checks every length against the bytes left before it is used; on false
+  // the object is as newly constructed (its disable_reassembly kept).
+  void save(std::string &out) const;
+  bool load(const uint8_t *src, size_t n);
 
  private:
   struct RIsuItem {  // RISUItem (decode/aerol.h:125-135)

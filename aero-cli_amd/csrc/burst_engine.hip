@@ -30,6 +30,8 @@
 #include "burst_engine.h"
 #include "engine_common.h"
 #include "host_pool.h"
+#include "chan_blob.h"
+#include "slot_copy.h"
 #include "slot_reset.h"
 #include "tables_host.h"
 
@@ -192,6 +194,9 @@ struct BurstGroup {
   int *d_reset_slots = nullptr;       // [2][C]: slots, scalar-init index
   bool reset_ready = false;
   uint64_t reset_launches = 0;        // aero_stat "slot_resets"
+  // aero_channel_export / aero_channel_import: the pack / unpack kernel's tables and staging
+  SlotCopier copier;
+  std::vector<ResetSeg> slot_plan;  // the pool's per-channel arrays (the reset plan), made with the copier
 };
 
 namespace {
@@ -605,6 +610,7 @@ void burst_group_destroy(BurstGroup *g) {
   if (g->d_reset_plan) (void)hipFree(g->d_reset_plan);
   if (g->d_reset_init) (void)hipFree(g->d_reset_init);
   if (g->d_reset_slots) (void)hipFree(g->d_reset_slots);
+  slot_copier_free(g->copier);
   if (g->pool) (void)hipFree(g->pool);
   if (g->st) (void)hipStreamDestroy(g->st);
   delete g;
@@ -967,6 +973,7 @@ int burst_dcd_edges(BurstGroup *g, int c, int64_t *edges) {
 uint64_t burst_stat(const BurstGroup *g, int which) {
   if (!g) return 0;
   if (which == 3) return g->reset_launches;
+  if (which == 4) return g->copier.launches;
   return which == 2 ? g->st_pass_max : (which ? g->st_packets : g->st_tests);
 }
 void burst_timing(BurstGroup *g, const char *name, double *ms, long *launches) {
@@ -986,6 +993,93 @@ int burst_sync(BurstGroup *g) {
   if (!g) return AERO_OK;
   BCHK(hipStreamSynchronize(g->st));
   return AERO_OK;
+}
+
+// ---- aero_channel_export / aero_channel_import (engine.hip) ----
+
+void burst_blob_plan(int kind, uint64_t *fingerprint, size_t *dev_bytes) {
+  LayoutRec rec;
+  burst_layout_plan(kind, 64, &rec);
+  const std::vector<ResetSeg> plan = reset_plan(rec);
+  *fingerprint = plan_fingerprint(plan);
+  *dev_bytes = (size_t)slot_bytes(plan);
+}
+
+bool burst_is_open(const BurstGroup *g, int c) { return g && c >= 0 && c < g->nch && !g->is_free[c]; }
+
+int burst_slots_left(const BurstGroup *g) { return g->C - g->nch + (int)g->free_slots.size(); }
+
+// the device state of every open channel is real (the scalar init of those
+// just opened, the reset of reused slots) and the stream idle
+int burst_export_begin(BurstGroup *g) {
+  BCHK(hipSetDevice(g->device));
+  if (int rc = flush_init(g)) return rc;
+  BCHK(hipStreamSynchronize(g->st));
+  return AERO_OK;
+}
+
+void burst_export_host(const BurstGroup *g, int c, std::string &out) {
+  BurstHost h;
+  h.avail = g->avail[c];
+  h.chunk_n = g->chunk_n[c];
+  h.hb_base = g->hb_base[c];
+  h.soft_seen = g->soft_seen[c];
+  h.tsu = g->tsu[c];
+  h.tblocks = g->tblocks[c];
+  h.ok_burst = g->ok_burst[c];
+  h.hops_seen = g->hops_seen[c];
+  h.since_run = g->since_run[c];
+  h.save(out, g->host[c].get());
+}
+
+// what burst_push and burst_run rely on: the pending samples inside the PCM
+// ring, the pending message starts inside theirs
+bool burst_host_fits(const BurstHost &h) {
+  return h.avail - h.hb_base <= B_PCM_CAP - 2 && h.since_run < CHUNK_RING;
+}
+
+static int burst_copy(BurstGroup *g, bool pack, const int *slots, int n, uint8_t *host) {
+  BCHK(hipSetDevice(g->device));
+  if (g->slot_plan.empty()) {
+    LayoutRec rec;
+    burst_layout_plan(g->kind, g->C, &rec);
+    if (rec.bad) return AERO_E_INVALID;
+    g->slot_plan = reset_plan(rec);
+  }
+  float ms = 0;
+  const bool timing = (g->flags & AERO_F_TIMING) != 0;
+  if (int rc = slot_copier_run(g->copier, g->st, pack, g->pool, g->C, g->slot_plan, slots, n, host,
+                               timing ? &ms : nullptr))
+    return rc;
+  if (timing) {
+    auto &t = g->timing[pack ? "slot_pack" : "slot_unpack"];
+    t.first += ms;
+    t.second++;
+  }
+  return AERO_OK;
+}
+
+int burst_pack(BurstGroup *g, const int *slots, int n, uint8_t *dst) { return burst_copy(g, true, slots, n, dst); }
+
+// after burst_open gave the slots out: their init or reset first (same
+// stream), then the packed states over them
+int burst_unpack(BurstGroup *g, const int *slots, int n, const uint8_t *src) {
+  BCHK(hipSetDevice(g->device));
+  if (int rc = flush_init(g)) return rc;
+  return burst_copy(g, false, slots, n, const_cast<uint8_t *>(src));
+}
+
+void burst_import_host(BurstGroup *g, int c, BurstHost &h) {
+  g->avail[c] = h.avail;
+  g->chunk_n[c] = h.chunk_n;
+  g->hb_base[c] = h.hb_base;
+  g->soft_seen[c] = h.soft_seen;
+  g->tsu[c] = h.tsu;
+  g->tblocks[c] = h.tblocks;
+  g->ok_burst[c] = h.ok_burst;
+  g->hops_seen[c] = h.hops_seen;
+  g->since_run[c] = h.since_run;
+  g->host[c] = std::move(h.host);
 }
 
 }  // namespace aero

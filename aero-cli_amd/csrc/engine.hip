@@ -25,6 +25,7 @@
 #include <condition_variable>
 #include <functional>
 #include <mutex>
+#include <new>
 #include <map>
 #include <memory>
 #include <string>
@@ -37,10 +38,12 @@
 #include "acars_host.h"
 #include "burst_engine.h"
 #include "aero_math.h"
+#include "chan_blob.h"
 #include "engine_common.h"
 #include "fft_layout.h"
 #include "host_pool.h"
 #include "engine_internal.h"
+#include "slot_copy.h"
 #include "slot_reset.h"
 #include "tables_host.h"
 
@@ -210,6 +213,10 @@ struct Group {
   hipEvent_t reset_ev = nullptr;  // after the last reset launch
   bool reset_done = false, reset_ready = false;
   uint64_t reset_launches = 0;  // aero_stat "slot_resets"
+  // aero_channel_export / aero_channel_import: the pack / unpack kernel's
+  // tables and staging (slot_copy.hip), made by the group's first export or import
+  SlotCopier copier;
+  std::vector<ResetSeg> slot_plan;  // the pool's per-channel arrays (the reset plan), made with the copier
   // host mirrors of the per-channel counters
   std::vector<long long> avail, nsamp, hops;
   std::vector<std::unique_ptr<PChannelHost>> host;
@@ -334,6 +341,7 @@ struct aero_engine {
   // engine channel -> (gid or MODE_BURST + kind, local index); (-1, -1): closed, its id in free_ids
   std::vector<std::pair<int, int>> chmap;
   std::set<int> free_ids;
+  std::vector<aero_channel_cfg> bcfg;  // by engine channel: a burst channel's cfg (a continuous one's is its group's)
   // aero_engine_reserve: channels a kind's group is created for, by (gid,
   // MODE_BURST + kind or generic-rate Mode, the generic rate's fs or 0)
   std::map<std::pair<int, int>, int> reserved;
@@ -343,7 +351,8 @@ struct aero_engine {
   }
   std::unique_ptr<HostPool> hpool;
   std::map<std::string, TimingSlot> timing;  // engine-level host sections
-  uint64_t retired_jobs = 0, retired_frames = 0, retired_su_ok = 0, retired_resets = 0;  // counters of released groups
+  uint64_t retired_jobs = 0, retired_frames = 0, retired_su_ok = 0, retired_resets = 0,
+           retired_copies = 0;  // counters of released groups
 };
 
 namespace {
@@ -1475,6 +1484,7 @@ void group_destroy(Group *e) {
   if (e->d_reset_slots) (void)hipFree(e->d_reset_slots);
   if (e->pin_reset_slots) (void)hipHostFree(e->pin_reset_slots);
   if (e->reset_ev) (void)hipEventDestroy(e->reset_ev);
+  slot_copier_free(e->copier);
   if (e->pin_stat) (void)hipHostFree(e->pin_stat);
   if (e->pin_pcm) (void)hipHostFree(e->pin_pcm);
   if (e->pin_pcm_ev) (void)hipEventDestroy(e->pin_pcm_ev);
@@ -1862,6 +1872,7 @@ void release_slot(aero_engine *e, int gid, int c) {
     e->retired_frames += g->st_frames.load();
     e->retired_su_ok += g->st_su_ok.load();
     e->retired_resets += g->reset_launches;
+    e->retired_copies += g->copier.launches;
     e->groups[gid].reset();
   }
 }
@@ -2052,6 +2063,63 @@ int kind_key(const aero_channel_cfg *cfg, int *key, int *gfs) {
   return AERO_OK;
 }
 
+// The packed slot of a channel kind in an engine of these flags: its layout
+// fingerprint and length (slot_copy.h), from the recorded layout alone (no
+// GPU).  *key / *gfs as kind_key gives them.
+int blob_plan(const aero_channel_cfg &cfg, int flags, uint64_t *fp, size_t *dev_bytes, int *key, int *gfs) {
+  if (int rc = kind_key(&cfg, key, gfs)) return rc;
+  if (*key >= MODE_BURST) {
+    burst_blob_plan(*key - MODE_BURST, fp, dev_bytes);
+    return AERO_OK;
+  }
+  const int mode = *gfs ? *key : (*key == GID_C8400 ? (int)MODE_C8400 : *key);
+  const ModeGeom g = *gfs ? msk_geom((int)cfg.bitrate, *gfs) : mode_geom(mode);
+  LayoutRec rec;
+  DevState S{};
+  DevTables T{};
+  layout(S, T, mode, g, 64, flags, nullptr, &rec);
+  if (rec.bad) return AERO_E_INVALID;
+  const std::vector<ResetSeg> plan = reset_plan(rec);
+  *fp = plan_fingerprint(plan);
+  *dev_bytes = (size_t)slot_bytes(plan);
+  return AERO_OK;
+}
+
+// one pack (pool -> host) or unpack launch for n sorted slots of the group
+int group_copy(Group *g, bool pack, const int *slots, int n, uint8_t *host) {
+  if (g->slot_plan.empty()) {
+    LayoutRec rec;
+    DevState S{};
+    DevTables T{};
+    layout(S, T, g->mode, g->g, g->C, g->flags, nullptr, &rec);
+    if (rec.bad) return AERO_E_INVALID;
+    g->slot_plan = reset_plan(rec);
+  }
+  float ms = 0;
+  const bool timing = (g->flags & AERO_F_TIMING) != 0;
+  if (int rc = slot_copier_run(g->copier, g->st, pack, g->pool, g->C, g->slot_plan, slots, n, host,
+                               timing ? &ms : nullptr))
+    return rc;
+  if (timing) {
+    auto &t = g->timing[tname(g, pack ? "slot_pack" : "slot_unpack")];
+    t.ms += ms;
+    t.launches++;
+  }
+  return AERO_OK;
+}
+
+// slots an open of this kind can still take before AERO_E_FULL (a generic-rate
+// MSK kind opens another group instead)
+int slots_left(aero_engine *e, int key, int gfs) {
+  if (key >= MODE_BURST) {
+    BurstGroup *b = e->burst[key - MODE_BURST];
+    return b ? burst_slots_left(b) : ((e->capacity(key, 0) + 63) & ~63);
+  }
+  if (gfs) return INT_MAX;
+  Group *g = e->groups[key].get();
+  return g ? g->C - g->nch + (int)g->free_slots.size() : ((e->capacity(key, 0) + 63) & ~63);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2120,6 +2188,8 @@ int aero_channel_open(aero_engine *e, const aero_channel_cfg *cfg, int *ch_out) 
     int local;
     if (int rc = burst_open(e->burst[kind], (int)cfg->bitrate, cfg->disable_reassembly != 0, &local)) return rc;
     *ch_out = take_id(e, key, local);
+    if (e->bcfg.size() <= (size_t)*ch_out) e->bcfg.resize((size_t)*ch_out + 1);
+    e->bcfg[*ch_out] = *cfg;
     return AERO_OK;
   }
   HIPCHK(hipSetDevice(e->device));
@@ -2171,6 +2241,201 @@ int aero_engine_reserve(aero_engine *e, const aero_channel_cfg *kind, int n) {
     return AERO_E_INVALID;
   }
   e->reserved[{key, gfs}] = n;
+  return AERO_OK;
+}
+
+int aero_channel_export(aero_engine *e, const int *ch, int n, void *dst, size_t cap, size_t *bytes) {
+  if (!e || n < 0 || (n && !ch) || !bytes) return AERO_E_INVALID;
+  for (int i = 0; i < n; i++)
+    if (ch[i] < 0 || ch[i] >= (int)e->chmap.size() || e->chmap[ch[i]].first < 0) return AERO_E_INVALID;
+  HIPCHK(hipSetDevice(e->device));
+  // Every group involved finishes what is queued, as for a close: the slots'
+  // pending init and resets, the queued host messages (into the PCM ring:
+  // they travel as ring rows), its passes and the host frame work.  Nothing is
+  // demodulated here, so no channel's output depends on when this happens.
+  std::set<int> kinds;
+  for (int i = 0; i < n; i++) kinds.insert(e->chmap[ch[i]].first);
+  for (int kind : kinds) {
+    if (kind >= MODE_BURST) {
+      if (int rc = burst_export_begin(e->burst[kind - MODE_BURST])) return rc;
+    } else {
+      Group *g = e->groups[kind].get();
+      if (int rc = flush_pending_init(g)) return rc;
+      if (int rc = hostq_flush(g)) return rc;
+      if (int rc = drain_group(g)) return rc;
+    }
+  }
+  host_wait(e);
+  HIPCHK(hipStreamSynchronize(nullptr));  // the trace collection's counter resets
+  struct Out {
+    aero_channel_cfg cfg;
+    uint64_t fp;
+    size_t dev_bytes, at;
+    std::string host;
+  };
+  std::vector<Out> out((size_t)n);
+  size_t total = 0;
+  for (int i = 0; i < n; i++) {
+    const int kind = e->chmap[ch[i]].first, c = e->chmap[ch[i]].second;
+    Out &o = out[i];
+    int key, gfs;
+    if (kind >= MODE_BURST) {
+      o.cfg = e->bcfg[ch[i]];
+      burst_export_host(e->burst[kind - MODE_BURST], c, o.host);
+    } else {
+      Group *g = e->groups[kind].get();
+      o.cfg = g->cfg[c];
+      ContHost h;
+      h.avail = g->avail[c];
+      h.nsamp = g->nsamp[c];
+      h.hops = g->hops[c];
+      h.hop_base = g->hop_base[c];
+      h.soft_seen = g->soft_seen[c];
+      h.pre_end = g->pre_end[c];
+      h.c_cd = g->c_cd[c];
+      h.c_dcd = g->c_dcd[c];
+      h.c_edges = g->c_edges[c];
+      h.msg_end = g->msg_end[c];
+      h.infofield = g->infofield[c];
+      h.save(o.host, g->host[c].get());
+    }
+    if (int rc = blob_plan(o.cfg, e->flags, &o.fp, &o.dev_bytes, &key, &gfs)) return rc;
+    o.at = total;
+    total += blob_size(o.dev_bytes, o.host.size());
+  }
+  *bytes = total;
+  if (!dst) return AERO_OK;
+  if (cap < total) return AERO_E_FULL;
+  uint8_t *d = static_cast<uint8_t *>(dst);
+  std::unique_ptr<uint8_t[]> stage;  // (not zero-filled: a batch of OQPSK channels is 1.9 MB each)
+  size_t stage_cap = 0;
+  for (int kind : kinds) {
+    // the group's channels of this call by slot: one launch packs them all
+    std::vector<std::pair<int, int>> list;
+    for (int i = 0; i < n; i++)
+      if (e->chmap[ch[i]].first == kind) list.push_back({e->chmap[ch[i]].second, i});
+    std::sort(list.begin(), list.end());
+    std::vector<int> slots;
+    for (auto &p : list) slots.push_back(p.first);
+    const size_t db = out[list[0].second].dev_bytes;
+    if (list.size() * db > stage_cap) {
+      stage_cap = list.size() * db;
+      stage.reset(new (std::nothrow) uint8_t[stage_cap]);
+      if (!stage) return AERO_E_NOMEM;
+    }
+    int rc;
+    if (kind >= MODE_BURST)
+      rc = burst_pack(e->burst[kind - MODE_BURST], slots.data(), (int)slots.size(), stage.get());
+    else
+      rc = group_copy(e->groups[kind].get(), true, slots.data(), (int)slots.size(), stage.get());
+    if (rc) return rc;
+    for (size_t k = 0; k < list.size(); k++) {
+      const Out &o = out[list[k].second];
+      uint8_t *dev = blob_write(d + o.at, o.cfg, (uint32_t)e->flags & BLOB_FLAGS, o.fp, o.dev_bytes, o.host);
+      memcpy(dev, stage.get() + k * db, db);
+    }
+  }
+  return AERO_OK;
+}
+
+int aero_channel_import(aero_engine *e, const void *src, size_t bytes, int *ch_out, int cap_ch, int *n) {
+  if (!e || (!src && bytes) || !ch_out || !n || cap_ch < 0) return AERO_E_INVALID;
+  *n = 0;
+  struct In {
+    BlobHeader h;
+    int key = 0, gfs = 0, id = -1;
+    ContHost cont;
+    BurstHost burst;
+  };
+  // every blob is parsed and checked before anything is opened or written
+  std::vector<In> in;
+  const uint8_t *p = static_cast<const uint8_t *>(src);
+  for (size_t pos = 0; pos < bytes;) {
+    in.emplace_back();
+    In &x = in.back();
+    if (!blob_parse(p + pos, bytes - pos, x.h)) return AERO_E_INVALID;
+    uint64_t fp;
+    size_t db;
+    if (blob_plan(x.h.cfg, e->flags, &fp, &db, &x.key, &x.gfs)) return AERO_E_INVALID;  // a kind open refuses
+    if (fp != x.h.fingerprint || db != x.h.dev_len) return AERO_E_INVALID;
+    if (x.h.flags != ((uint32_t)e->flags & BLOB_FLAGS)) return AERO_E_INVALID;
+    if (x.key >= MODE_BURST) {
+      if (!x.burst.load(x.h.host, (size_t)x.h.host_len) || !burst_host_fits(x.burst)) return AERO_E_INVALID;
+    } else {
+      if (!x.cont.load(x.h.host, (size_t)x.h.host_len)) return AERO_E_INVALID;
+      if (x.cont.avail - x.cont.nsamp > PCM_CAP - 2) return AERO_E_INVALID;  // more pending than the ring holds
+    }
+    pos += (size_t)x.h.total;
+  }
+  if (in.size() > (size_t)cap_ch) return AERO_E_FULL;
+  {
+    std::map<std::pair<int, int>, int> want;
+    for (const In &x : in) want[{x.key, x.gfs}]++;
+    for (const auto &w : want)
+      if (w.second > slots_left(e, w.first.first, w.first.second)) return AERO_E_FULL;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  // all or nothing: a failure below closes what this call opened
+  auto undo = [&](int rc) {
+    for (In &x : in)
+      if (x.id >= 0) (void)aero_channel_close(e, x.id);
+    return rc;
+  };
+  for (In &x : in)
+    if (int rc = aero_channel_open(e, &x.h.cfg, &x.id)) return undo(rc);
+  host_wait(e);
+  std::set<int> kinds;
+  for (const In &x : in) kinds.insert(e->chmap[x.id].first);
+  std::unique_ptr<uint8_t[]> stage;  // (not zero-filled: a batch of OQPSK channels is 1.9 MB each)
+  size_t stage_cap = 0;
+  for (int kind : kinds) {
+    std::vector<std::pair<int, int>> list;  // (slot, blob), by slot: one launch unpacks them all
+    for (size_t i = 0; i < in.size(); i++)
+      if (e->chmap[in[i].id].first == kind) list.push_back({e->chmap[in[i].id].second, (int)i});
+    std::sort(list.begin(), list.end());
+    std::vector<int> slots;
+    for (auto &q : list) slots.push_back(q.first);
+    const size_t db = (size_t)in[list[0].second].h.dev_len;
+    if (list.size() * db > stage_cap) {
+      stage_cap = list.size() * db;
+      stage.reset(new (std::nothrow) uint8_t[stage_cap]);
+      if (!stage) return undo(AERO_E_NOMEM);
+    }
+    for (size_t k = 0; k < list.size(); k++) memcpy(stage.get() + k * db, in[list[k].second].h.dev, db);
+    if (kind >= MODE_BURST) {
+      BurstGroup *b = e->burst[kind - MODE_BURST];
+      if (int rc = burst_unpack(b, slots.data(), (int)slots.size(), stage.get())) return undo(rc);
+      for (auto &q : list) burst_import_host(b, q.first, in[q.second].burst);
+      continue;
+    }
+    Group *g = e->groups[kind].get();
+    // the new slots' scalar init, and the reset of reused ones, are launched
+    // first on the group's stream; the unpack follows them there
+    if (int rc = flush_pending_init(g)) return undo(rc);
+    if (int rc = group_copy(g, false, slots.data(), (int)slots.size(), stage.get())) return undo(rc);
+    for (auto &q : list) {
+      const int c = q.first;
+      ContHost &h = in[q.second].cont;
+      g->avail[c] = h.avail;
+      g->nsamp[c] = h.nsamp;
+      g->hops[c] = h.hops;
+      g->hop_base[c] = h.hop_base;
+      g->soft_seen[c] = h.soft_seen;
+      g->pre_end[c] = h.pre_end;
+      g->c_cd[c] = h.c_cd;
+      g->c_dcd[c] = h.c_dcd;
+      g->c_edges[c] = h.c_edges;
+      g->msg_end[c] = std::move(h.msg_end);
+      g->infofield[c] = std::move(h.infofield);
+      g->host[c] = std::move(h.host);
+    }
+    // ring rows the imported channels have pending were never seen by this
+    // group's demod launches: a device push waits for the stream instead
+    for (auto &pr : g->consumed) g->ev_free.push_back(pr.second);
+    g->consumed.clear();
+  }
+  for (size_t i = 0; i < in.size(); i++) ch_out[i] = in[i].id;
+  *n = (int)in.size();
   return AERO_OK;
 }
 
@@ -2467,8 +2732,15 @@ int aero_stat(aero_engine *e, const char *name, uint64_t *value) {
   uint64_t v = 0;
   const std::string n(name);
   if (n != "rt_tests" && n != "rt_packets" && n != "rt_pass_max" && n != "viterbi_jobs" && n != "frames" &&
-      n != "su_crc_ok" && n != "device_bytes" && n != "groups" && n != "slot_resets")
+      n != "su_crc_ok" && n != "device_bytes" && n != "groups" && n != "slot_resets" && n != "slot_copies")
     return AERO_E_INVALID;
+  if (n == "slot_copies") {  // launches of the pack / unpack kernels (one per export or import and group)
+    v = e->retired_copies + burst_stat(e->burst[0], 4) + burst_stat(e->burst[1], 4);
+    for (auto &g : e->groups)
+      if (g) v += g->copier.launches;
+    *value = v;
+    return AERO_OK;
+  }
   if (n == "slot_resets") {  // launches of the reset kernel (one per batch of closed slots and group)
     v = e->retired_resets + burst_stat(e->burst[0], 3) + burst_stat(e->burst[1], 3);
     for (auto &g : e->groups)
@@ -2669,18 +2941,8 @@ extern "C" void aero_x_viterbi_stamps(unsigned long long *out4) { viterbi_read_s
 // the burst OQPSK demod's per-section cycle totals (AERO_X_BSTAMPS build; burst.hip)
 extern "C" void aero_x_burst_stamps(unsigned long long *out16) { burst_read_stamps(out16); }
 
-// host check (tests/test_channel_lifecycle_host.py; no GPU): the reset plan
-// of slot `slot` in a pool of C channels, as the reset kernel addresses it.
-// kind: a Mode (MODE_C8400 included), a generic-rate MSK Mode | fs << 8, or
-// 100 + BurstKind.  Records of 7 uint64: byte offset of the slot's first
-// row, bytes per row, rows, row pitch, ResetKind, ResetFill, bytes of the
-// whole array.  slot -1: every array of the layout instead (offset of the
-// array; ResetKind 0 for what belongs to no slot), then one record of
-// ResetKind 3 whose offset is the pool size.  Returns the record count (at
-// most `cap` are written) or a negative AERO_E_*.
-extern "C" int aero_x_reset_plan(int kind, int C, int flags, int slot, uint64_t *out, int cap) {
-  if (C < 64 || C % 64 || slot < -1 || slot >= C || (cap && !out)) return AERO_E_INVALID;
-  LayoutRec rec;
+// the recorded layout of a pool of C channels of an aero_x_reset_plan kind (below); *pool_out: its size
+static int x_layout(int kind, int C, int flags, LayoutRec &rec, size_t *pool_out) {
   size_t pool = 0;
   if (kind == 100 || kind == 101) {
     pool = burst_layout_plan(kind - 100, C, &rec);
@@ -2701,6 +2963,24 @@ extern "C" int aero_x_reset_plan(int kind, int C, int flags, int slot, uint64_t 
     pool = layout(S, T, mode, g, C, flags, nullptr, &rec);
   }
   if (rec.bad) return AERO_E_INVALID;
+  *pool_out = pool;
+  return AERO_OK;
+}
+
+// host check (tests/test_channel_lifecycle_host.py; no GPU): the reset plan
+// of slot `slot` in a pool of C channels, as the reset kernel addresses it.
+// kind: a Mode (MODE_C8400 included), a generic-rate MSK Mode | fs << 8, or
+// 100 + BurstKind.  Records of 7 uint64: byte offset of the slot's first
+// row, bytes per row, rows, row pitch, ResetKind, ResetFill, bytes of the
+// whole array.  slot -1: every array of the layout instead (offset of the
+// array; ResetKind 0 for what belongs to no slot), then one record of
+// ResetKind 3 whose offset is the pool size.  Returns the record count (at
+// most `cap` are written) or a negative AERO_E_*.
+extern "C" int aero_x_reset_plan(int kind, int C, int flags, int slot, uint64_t *out, int cap) {
+  if (C < 64 || C % 64 || slot < -1 || slot >= C || (cap && !out)) return AERO_E_INVALID;
+  LayoutRec rec;
+  size_t pool = 0;
+  if (int rc = x_layout(kind, C, flags, rec, &pool)) return rc;
   std::vector<ResetSeg> segs = slot < 0 ? rec.segs : reset_plan(rec);
   if (slot < 0) {
     ResetSeg end{};
@@ -2718,6 +2998,42 @@ extern "C" int aero_x_reset_plan(int kind, int C, int flags, int slot, uint64_t 
     k++;
   }
   return k;
+}
+
+// host checks (tests/test_channel_blob_host.py; no GPU) of the pack / unpack
+// addressing, over a host copy `pool` of a pool of C channels of an
+// aero_x_reset_plan kind: the plain C++ form of the kernels (slot_copy.h
+// pack_slot_host / unpack_slot_host).  pack: slot -> blob, the device section
+// of a channel blob; unpack: blob -> slot.  Both return the section's length
+// (pack with blob == NULL only that), or a negative AERO_E_*.
+extern "C" long long aero_x_slot_pack(int kind, int C, int flags, int slot, const void *pool, void *blob) {
+  if (C < 64 || C % 64 || slot < 0 || slot >= C || (blob && !pool)) return AERO_E_INVALID;
+  LayoutRec rec;
+  size_t size = 0;
+  if (int rc = x_layout(kind, C, flags, rec, &size)) return rc;
+  const std::vector<ResetSeg> plan = reset_plan(rec);
+  if (blob) pack_slot_host(plan, static_cast<const uint8_t *>(pool), slot, static_cast<uint8_t *>(blob));
+  return (long long)slot_bytes(plan);
+}
+
+extern "C" long long aero_x_slot_unpack(int kind, int C, int flags, int slot, void *pool, const void *blob) {
+  if (C < 64 || C % 64 || slot < 0 || slot >= C || !pool || !blob) return AERO_E_INVALID;
+  LayoutRec rec;
+  size_t size = 0;
+  if (int rc = x_layout(kind, C, flags, rec, &size)) return rc;
+  const std::vector<ResetSeg> plan = reset_plan(rec);
+  unpack_slot_host(plan, static_cast<uint8_t *>(pool), slot, static_cast<const uint8_t *>(blob));
+  return (long long)slot_bytes(plan);
+}
+
+// the layout fingerprint a channel blob of this kind carries (slot_copy.h plan_fingerprint)
+extern "C" int aero_x_plan_fingerprint(int kind, int C, int flags, uint64_t *out) {
+  if (C < 64 || C % 64 || !out) return AERO_E_INVALID;
+  LayoutRec rec;
+  size_t size = 0;
+  if (int rc = x_layout(kind, C, flags, rec, &size)) return rc;
+  *out = plan_fingerprint(reset_plan(rec));
+  return AERO_OK;
 }
 
 // host check (tests/test_abi.py): the constants a generic-rate MSK group

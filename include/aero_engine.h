@@ -119,6 +119,69 @@ int aero_channel_open(aero_engine *e, const aero_channel_cfg *cfg, int *ch_out);
  * released when its last channel leaves. */
 int aero_channel_close(aero_engine *e, int ch);
 
+/* Snapshot of n channels' decoder state as n self-delimiting blobs written
+ * back to back (ch[i]'s blob is the i-th).  dst == NULL: *bytes = the size
+ * needed, nothing else happens to dst.  cap too small: AERO_E_FULL, nothing
+ * written (*bytes is still the size needed).  A closed or out-of-range id:
+ * AERO_E_INVALID.
+ *
+ * An export is a snapshot, not a close: the channel stays open and carries on
+ * exactly as if nothing had happened, and no channel's output changes by one
+ * bit.  A move is export, the caller's pops, aero_channel_close, and
+ * aero_channel_import on the other engine (another GPU, another process, a
+ * later run of the program: a blob may be kept in a file).
+ *
+ * What travels is everything that decides the channel's future output: every
+ * byte its slot owns in the group's device pool (AGC ring, loops, coarse
+ * history, AFC / hunter, AeroL framing and DCD, the PCM ring with the samples
+ * pushed and not yet demodulated: a partial hop, a C-channel message not yet
+ * prefiltered, a burst message pushed since the last run), the host counters
+ * (so hop sample indices, soft-bit positions, dcd_edges and hunter_steps
+ * continue their numbering), the half-assembled ISUs and ACARS messages, and
+ * the channel's aero_channel_cfg.  What does not: outputs produced and not yet
+ * popped (items, soft bits, hops, pt, blocks, frames, R/T tests and packets, C
+ * units, voice) stay with the source channel.
+ *
+ * The channels' groups first finish what is queued, as aero_channel_close
+ * does: the pending init / reset of slots, their GPU passes and host frame
+ * work; host messages queued by aero_push_pcm are moved to the PCM ring.
+ * Nothing is demodulated.  One launch of the pack kernel per group and call,
+ * however many channels (aero_stat "slot_copies").
+ *
+ * The blob (little-endian): 8-byte magic "AEROCHB1", u32 version, the
+ * channel's cfg as i32 bitrate, i32 burst, u32 fs, i32 disable_reassembly,
+ * u32 decode-shaping engine flags, u64 layout fingerprint, u64 total length,
+ * u64 length + device section, u64 length + host section.  Only the version
+ * that wrote a blob reads it. */
+int aero_channel_export(aero_engine *e, const int *ch, int n, void *dst, size_t cap, size_t *bytes);
+
+/* Opens one channel per blob of src (ids and slots as aero_channel_open gives
+ * them: the smallest free first) and installs the exported state; ch_out[i] =
+ * the id of blob i, *n = the number of blobs.  The channels continue where the
+ * exported ones were: pushing the rest of the stream gives, bit for bit, what
+ * the uninterrupted channel would have given.  One blob may be imported more
+ * than once (each import is its own channel).
+ *
+ * Admission is aero_channel_open's: AERO_E_FULL when the kind's group or
+ * reserved pool has too few free slots for the batch (or cap_ch < blobs); a
+ * generic-rate MSK group or the C group is created on first use.
+ * AERO_E_INVALID, before anything is opened or written, for a blob whose
+ * magic, version or total length is wrong, whose section lengths run past
+ * `bytes`, whose kind aero_channel_open refuses, whose layout fingerprint
+ * differs from this engine's for the kind (a hash over the kinds, element
+ * sizes, rows and fills of the per-channel arrays; not their offsets or the
+ * group's size, which may differ), or whose decode-shaping flags differ from
+ * the engine's (AERO_F_TRACE_PT, AERO_F_TRACE_BLOCKS, AERO_F_DCD_TICK; the
+ * parity traces AERO_F_TRACE_SOFT and AERO_F_TRACE_HOPS are not checked, but
+ * continue their numbering only between engines that both keep them).  Every
+ * length is checked before it is used.  A batch is all or nothing: on any
+ * error no channel of it stays open.
+ *
+ * The states are written by one launch of the unpack kernel per group and
+ * call, ordered on the group's stream after the init or pending reset of the
+ * slots they land in; the call returns when it has finished. */
+int aero_channel_import(aero_engine *e, const void *src, size_t bytes, int *ch_out, int cap_ch, int *n);
+
 /* Declares that the engine will hold at most n channels of `kind`
  * (bitrate / burst / fs as for aero_channel_open) at once: the kind's group
  * is then created with n slots (rounded up to 64, as max_channels is)
@@ -238,7 +301,8 @@ void aero_timing_reset(aero_engine *e);
  * channels: "rt_tests" (RTChannelDeleaveFECScram decodes run),
  * "rt_packets" (R/T packets that passed their CRCs), "rt_pass_max" (the most
  * R/T tests one pass handed to the host; from 256 on they are split over the
- * host threads); "slot_resets": launches of the kernel that resets closed
+ * host threads); "slot_copies": launches of the kernels that pack and unpack
+ * exported / imported slots; "slot_resets": launches of the kernel that resets closed
  * channels' slots (one per group for all the slots closed since the group
  * last pushed or ran).  Joins the
  * asynchronous host frame work first.  AERO_E_INVALID for another name. */

@@ -7,6 +7,7 @@
 // tables with the oracle's; built plain and, by `build.py --asan`, with
 // AddressSanitizer + UndefinedBehaviorSanitizer.
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../aero-cli_amd/csrc/acars_host.h"
@@ -30,6 +31,15 @@ size_t hc_items(void *h, aero_acars_item *dst, size_t cap) {
   v.erase(v.begin(), v.begin() + (long)n);
   return n;
 }
+// PChannelHost::save into dst (at most cap bytes are written); returns the state's size
+size_t hc_save(void *h, uint8_t *dst, size_t cap) {
+  std::string s;
+  static_cast<aero::PChannelHost *>(h)->save(s);
+  if (dst && cap) memcpy(dst, s.data(), s.size() < cap ? s.size() : cap);
+  return s.size();
+}
+// PChannelHost::load: 1 when the state was taken, 0 when it was refused (h is then as a new host)
+int hc_load(void *h, const uint8_t *src, size_t n) { return static_cast<aero::PChannelHost *>(h)->load(src, n) ? 1 : 0; }
 
 void hc_cis(double *cis) { aero::host_cis(cis); }
 void hc_twiddles(int nfft, double *tw, double *twi) { aero::host_twiddles(nfft, tw, twi); }
