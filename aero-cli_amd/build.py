@@ -44,11 +44,15 @@ CXX_SRCS = ['tables_host.cpp', 'acars_host.cpp', 'chan_blob.cpp']
 # With the RRC partial sums on the helper wave, machine LICM's hoisted FP64
 # constants are what spills (211 SGPRs -> VGPR lanes; 15 without it):
 # 13.76 -> 12.83 ms (profiles/r04/ab/g8_licm.txt).
+# The persistent coarse kernel walks through its channels in a loop; machine
+# LICM hoists the libm ports' FP64 constants over the whole walk, transforms
+# included (29 SGPR and 14 VGPR spills in the OQPSK instance; none without it).
 FILE_FLAGS = {'burst.hip': ['-mllvm', '-disable-machine-licm'],
               'burst_msk.hip': ['-mllvm', '-disable-machine-licm'],
               'demod_oqpsk.hip': ['-mllvm', '--amdgpu-sched-strategy=max-memory-clause', '-mllvm',
                                   '-disable-machine-licm'],
-              'cchan.hip': ['-mllvm', '-disable-machine-licm']}
+              'cchan.hip': ['-mllvm', '-disable-machine-licm'],
+              'coarse.hip': ['-mllvm', '-disable-machine-licm']}
 
 
 def _run(cmd):
@@ -113,6 +117,17 @@ def build_fftsim():
     if _stale(FFTSIM_SO, [src, os.path.join(CSRC, 'fft_layout.h')]):
         _run(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-o', FFTSIM_SO, src])
     return FFTSIM_SO
+
+
+SCHEDSIM_SO = os.path.join(ROOT, 'tools', 'libcoarse_sched_sim.so')
+
+
+def build_schedsim():
+    """Test-only host model of the persistent coarse kernel's channel schedule (tests/test_coarse_sched.py)."""
+    src = os.path.join(ROOT, 'tools', 'coarse_sched_sim.cpp')
+    if _stale(SCHEDSIM_SO, [src, os.path.join(CSRC, 'coarse_sched.h')]):
+        _run(['g++', '-O2', '-std=c++17', '-Wall', '-fPIC', '-shared', '-o', SCHEDSIM_SO, src])
+    return SCHEDSIM_SO
 
 
 def build_mathhost():
@@ -240,6 +255,7 @@ def build_all(jobs=4):
     build_synth()
     build_mathhost()
     build_fftsim()
+    build_schedsim()
     build_hostcheck()
     so = build_engine(jobs)
     build_diag(jobs)

@@ -57,7 +57,7 @@ void demod_read_stamps(unsigned long long *);
 void coarse_read_stamps(unsigned long long *);
 void viterbi_read_stamps(unsigned long long *);
 void burst_read_stamps(unsigned long long *);
-void launch_coarse(hipStream_t, int, const DevState &, const DevTables &, int);
+void launch_coarse(hipStream_t, int, const DevState &, const DevTables &, int, int);
 void launch_frame(hipStream_t, int, const DevState &, int);
 void launch_viterbi(hipStream_t, int, const DevState &, const DevTables &, int, int);
 // the C channel (cchan.hip)
@@ -189,6 +189,9 @@ struct Group {
   // demod_msk.hip) run while nch <= wide_max (AERO_OQPSK_WIDE /
   // AERO_MSK_WIDE, default WIDE_MAX_DEFAULT; 0: never)
   int wide_max = 0;
+  // the persistent coarse kernel's workgroup limit (coarse.hip; OQPSK and the
+  // C channel): the device's CU count, or AERO_COARSE_GRID
+  int coarse_grid = 1;
   ModeGeom g{};
   int device = 0, flags = 0, C = 0, nch = 0;
   std::string tag;  // timing-name prefix ("" for OQPSK, "msk600_", "msk1200_", "msk600_48k_", "msk600_16000_", ...)
@@ -1058,7 +1061,7 @@ int run_pass(Group *e, int flush, bool *more) {
     hipEvent_t a, b;
     if (any_hop) {
       ev_begin(e, "coarse", a, b);
-      launch_coarse(e->st, e->mode, e->S, e->T, e->nch);
+      launch_coarse(e->st, e->mode, e->S, e->T, e->nch, e->coarse_grid);
       ev_end(e, b);
     }
     if (int rc = issue_viterbi(e)) return rc;  // the previous pass's decode, before this demod
@@ -1273,6 +1276,13 @@ int group_create(aero_engine *E, int mode, int gid, int fs, std::unique_ptr<Grou
   {
     const char *w = getenv(mode == MODE_OQPSK ? "AERO_OQPSK_WIDE" : "AERO_MSK_WIDE");
     e->wide_max = w ? atoi(w) : WIDE_MAX_DEFAULT;
+    const char *cg = getenv("AERO_COARSE_GRID");
+    int cus = 0;
+    if (cg)
+      cus = atoi(cg);
+    else
+      HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
+    e->coarse_grid = std::max(cus, 1);
   }
   if (msk_generic(mode)) {
     e->g = msk_geom(msk_bitrate(mode), fs);

@@ -1,6 +1,6 @@
 /*
  * fft_chain.h — the coarse estimator's three chained JFFT transforms
- * (forward, inverse, forward: decode/coarsefreqestimate.cpp:134-160, JFFT
+ * (forward, inverse, forward: decode/coarsefreqestimate.cpp:95-110, JFFT
  * decode/jfft.cpp:114-212) for one 2^L-point channel-hop per workgroup of
  * 2^(L-4) threads on gfx950, 16 complex FP64 values per thread.
  *

@@ -1,5 +1,8 @@
 """Diagnostic: per-section cycle totals of the coarse FFT kernel (wave 0 of
-every workgroup that ran a hop) from the AERO_X_STAMPS build.
+every workgroup that ran a hop) from the AERO_X_STAMPS build: the sections of
+a hop, lane 0's hop control, and what is left of the workgroup's time in the
+kernel (the turnover between channels: launch, batch scans, waits for the
+other waves at a channel's first barrier).
 Usage: AERO_ENGINE_SO=aero-cli_amd/libaero_engine_stamps.so python scripts/coarse_stamps.py [channels]"""
 import ctypes
 import os
@@ -29,9 +32,9 @@ out = (ctypes.c_ulonglong * 12)()
 vfn = lib.aero_x_viterbi_stamps
 vfn.argtypes = [ctypes.c_void_p]
 vout = (ctypes.c_ulonglong * 4)()
-names = ['prologue', 'ring to LDS + twiddles', 'table gathers + mix', 'FFT 1', 'boxcar+iFFT+square', 'FFT 3',
-         'hypot', 'log10 smoothing', 'fold search']
-order = list(range(9))
+names = ['batch scan + state', 'ring to LDS', 'table gathers + mix', 'FFT 1', 'boxcar+iFFT+square', 'FFT 3',
+         'hypot', 'log10 + next loads', 'fold search', 'hop control (lane 0)']
+order = list(range(10))
 for s in range(steps):
     views = [pool[:, int(o) + s * 4096:int(o) + (s + 1) * 4096] for o in offs]
     x = torch.stack(views).permute(2, 0, 1).reshape(4096, C).contiguous()
@@ -44,11 +47,13 @@ for s in range(steps):
         vfn(vout)
 fn(out)
 vfn(vout)
-tot = sum(out[:9])
+tot = sum(out[:10])
 n = out[11]
 print('channels %d, hops %d, s_memtime cycles per hop (wave 0) %.0f' % (C, n, tot / max(n, 1)))
 for k in order:
     print('  %-20s %9.0f  %5.1f %%' % (names[k], out[k] / max(n, 1), 100.0 * out[k] / max(tot, 1)))
+if out[10]:  # the persistent kernel: wave 0's whole time in the kernel
+    print('  %-20s %9.0f  (kernel time per hop %.0f)' % ('turnover', (out[10] - tot) / max(n, 1), out[10] / max(n, 1)))
 eng.close()
 vn = vout[3]
 print('viterbi jobs %d, s_memtime cycles per job %.0f' % (vn, sum(vout[:3]) / max(vn, 1)))
