@@ -157,6 +157,13 @@ _SIGS = {
     'aero_chan_pop_iq': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                         ctypes.POINTER(ctypes.c_size_t)]),
     'aero_chan_feed': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
+    'aero_chan_vfo_open': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ChanVfo), ctypes.POINTER(ctypes.c_int)]),
+    'aero_chan_vfo_close': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'aero_chan_vfo_skip': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    'aero_chan_reserve': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ChanVfo), ctypes.c_int]),
+    'aero_chan_vfo_count': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
+    'aero_chan_vfo_settle': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'aero_chan_stat': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 _lib = None
@@ -597,9 +604,7 @@ class Channeliser:
                             int(d.get('publish', 0)))
         v = (ChanVfo * max(1, len(vfos)))()
         for i, d in enumerate(vfos):
-            v[i] = ChanVfo(int(d['frequency']), int(d.get('data_rate', 0)), int(d.get('out_rate', 0)),
-                           int(d.get('filter_bandwidth', 0)), float(d.get('gain', 0.0)),
-                           int(bool(skip[i])) if skip is not None else 0)
+            v[i] = self._vfo(d, skip[i] if skip is not None else False)
         h = ctypes.c_void_p()
         _check(self.lib.aero_chan_create(ctypes.byref(cfg), m, len(mains), v, len(vfos), ctypes.byref(h)),
                'aero_chan_create')
@@ -676,6 +681,55 @@ class Channeliser:
         return self._pop(self.lib.aero_chan_pop_iq, m, np.int8)
 
     def feed(self, engine, channels):
-        """channels[v]: engine channel of [vfos] entry v, or -1."""
-        arr = (ctypes.c_int * max(1, self.nvfo))(*[int(c) for c in channels])
+        """channels[v]: engine channel of [vfos] entry v, or -1; vfo_count() entries."""
+        n = self.vfo_count()
+        if len(channels) < n:
+            raise ValueError('feed needs one channel (or -1) for each of the %d [vfos] ids' % n)
+        arr = (ctypes.c_int * max(1, n))(*[int(c) for c in channels[:n]])
         _check(self.lib.aero_chan_feed(self.h, engine.h, arr), 'aero_chan_feed')
+
+    # ---- [vfos] entries while the receiver runs (include/aero_chan.h)
+    @staticmethod
+    def _vfo(d, skip=False):
+        return ChanVfo(int(d['frequency']), int(d.get('data_rate', 0)), int(d.get('out_rate', 0)),
+                       int(d.get('filter_bandwidth', 0)), float(d.get('gain', 0.0)), int(bool(skip)))
+
+    def open_vfo(self, vfo, skip=False):
+        """Adds the [vfos] entry `vfo` (a dict as in the constructor); returns its id, the smallest
+        free one.  It takes part from the next read pushed, with zero filter histories and the NCO
+        phase of the reads taken so far: after settle(id) samples its audio is that of an entry that
+        was always there.  Reads pushed and not yet run are run first."""
+        v = ctypes.c_int()
+        _check(self.lib.aero_chan_vfo_open(self.h, ctypes.byref(self._vfo(vfo, skip)), ctypes.byref(v)),
+               'aero_chan_vfo_open')
+        return v.value
+
+    def close_vfo(self, v):
+        """Removes entry v; its slot is reused by the next start of the same shape."""
+        _check(self.lib.aero_chan_vfo_close(self.h, v), 'aero_chan_vfo_close')
+
+    def skip_vfo(self, v, skip=True):
+        """Sets or clears entry v's skip flag (another process computes it); the id stays."""
+        _check(self.lib.aero_chan_vfo_skip(self.h, v, int(bool(skip))), 'aero_chan_vfo_skip')
+
+    def reserve(self, like, n):
+        """Pre-allocates n free slots of the shape the entry `like` resolves to."""
+        _check(self.lib.aero_chan_reserve(self.h, ctypes.byref(self._vfo(like)), int(n)), 'aero_chan_reserve')
+
+    def vfo_count(self):
+        """One past the largest [vfos] id in use: the length feed() expects."""
+        n = ctypes.c_int()
+        _check(self.lib.aero_chan_vfo_count(self.h, ctypes.byref(n)), 'aero_chan_vfo_count')
+        return n.value
+
+    def settle(self, v):
+        """Output samples after a start within which entry v may differ from one that was always there."""
+        n = ctypes.c_size_t()
+        _check(self.lib.aero_chan_vfo_settle(self.h, v, ctypes.byref(n)), 'aero_chan_vfo_settle')
+        return int(n.value)
+
+    def stat(self, name):
+        """aero_chan_stat: 'device_bytes', 'vfo_inits' (start-kernel launches) or 'slots_free'."""
+        v = ctypes.c_uint64()
+        _check(self.lib.aero_chan_stat(self.h, name.encode(), ctypes.byref(v)), 'aero_chan_stat')
+        return int(v.value)

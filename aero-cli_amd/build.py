@@ -130,6 +130,17 @@ def build_schedsim():
     return SCHEDSIM_SO
 
 
+CHANSLOTS_SO = os.path.join(ROOT, 'tools', 'libchan_slots_sim.so')
+
+
+def build_chanslots():
+    """Test-only host walk of the channeliser's run-time VFO bookkeeping (tests/test_chan_start_model.py)."""
+    src = os.path.join(ROOT, 'tools', 'chan_slots_sim.cpp')
+    if _stale(CHANSLOTS_SO, [src, os.path.join(CSRC, 'chan_slots.h')]):
+        _run(['g++', '-O2', '-std=c++17', '-Wall', '-fPIC', '-shared', '-o', CHANSLOTS_SO, src])
+    return CHANSLOTS_SO
+
+
 def build_mathhost():
     src = os.path.join(ROOT, 'tools', 'mathhost.cpp')
     deps = [src, os.path.join(CSRC, 'aero_math.h'), os.path.join(CSRC, 'aero_glibc_tables.h')]
@@ -256,6 +267,7 @@ def build_all(jobs=4):
     build_mathhost()
     build_fftsim()
     build_schedsim()
+    build_chanslots()
     build_hostcheck()
     so = build_engine(jobs)
     build_diag(jobs)

@@ -23,6 +23,13 @@
  * The only recurrence, the optional DC removal (publisher.cpp:292-296), runs
  * in one lane per arm.
  *
+ * [vfos] entries come and go while the receiver runs (aero_chan_vfo_open /
+ * _close / _skip).  A running sub-VFO owns a slot: its device buffers and the
+ * constant data of its shape (chan_slots.h).  A VFO that starts gets zero
+ * histories and its NCO table from start_kernel, once per batch of starts,
+ * and its NCO index is a function of the reads the channeliser has taken, so
+ * its output does not depend on when it was opened.
+ *
  * These kernels are HBM/launch bound (a few flops per byte); the grid spans
  * reads x tiles x VFOs so one launch per stage level fills the chip.
  */
@@ -38,6 +45,7 @@
 #include <vector>
 
 #include "../../include/aero_chan.h"
+#include "chan_slots.h"
 #include "engine_internal.h"
 #include "tables_host.h"
 
@@ -45,6 +53,8 @@ using aero::host_pub_hilbert;
 using aero::host_pub_low_pass;
 using aero::host_pub_osc;
 using aero::host_pub_osc_len;
+using aero::host_pub_osc_rotation;
+namespace cslots = aero::cslots;
 
 namespace {
 
@@ -245,29 +255,101 @@ __global__ __launch_bounds__(256) void shift_kernel(const ShiftJob *jobs) {
   for (int i = threadIdx.x; i < s.h; i += 256) s.base[i] = s.base[s.len + i];
 }
 
+struct StartJob {  // one VFO that starts with the next read
+  float2 *osc;            // 1-second NCO table to fill; nullptr: a main VFO (half-band history only)
+  float2 *hist0, *hist1;  // both parities, MAX_STAGES * 11 each
+  float2 *zext, *wext;    // history heads: nlate, HIL_H (nullptr: none)
+  float *uext;            // history head: nusb
+  int osc_len, nlate, nusb;
+  float rot_re, rot_im;   // (float)cos, (float)sin of the angle per sample, from the host
+};
+
+constexpr int START_LANES = 64, START_VFOS = 8, OSC_GATHER = 8;
+
+// Starts START_VFOS VFOs per wave.  All lanes zero the histories job by job;
+// then one lane owns one VFO and runs Oscillator::Oscillator's serial FP32
+// recurrence (oscillator.cpp:4-28, as tables_host.cpp's host_pub_osc): rotate,
+// renormalise by 1.95 - |v|^2.  The lanes write to different tables, so each
+// gathers OSC_GATHER entries (64 B) and stores them as four 16-byte words.
+// The recurrence is a dependent chain (36 ns per entry, 6.9 ms per 192000-entry
+// table however many lanes run it); every store instruction touches one line
+// per lane, and with 64 tables in one wave those stores cost more than the
+// chain (16 ms for 64 VFOs), with 8 they hide under it (7.0 ms).
+__global__ __launch_bounds__(START_LANES) void start_kernel(const StartJob *jobs, int njobs) {
+  const int lane = threadIdx.x, j0 = blockIdx.x * START_VFOS;
+  const int nj = min(START_VFOS, njobs - j0);
+  const float2 z2 = make_float2(0.f, 0.f);
+  for (int q = 0; q < nj; q++) {
+    const StartJob &j = jobs[j0 + q];
+    for (int i = lane; i < MAX_STAGES * 11; i += START_LANES) j.hist0[i] = j.hist1[i] = z2;
+    if (j.zext)
+      for (int i = lane; i < j.nlate; i += START_LANES) j.zext[i] = z2;
+    if (j.wext)
+      for (int i = lane; i < HIL_H; i += START_LANES) j.wext[i] = z2;
+    if (j.uext)
+      for (int i = lane; i < j.nusb; i += START_LANES) j.uext[i] = 0.f;
+  }
+  if (lane >= nj) return;
+  const StartJob j = jobs[j0 + lane];
+  if (!j.osc) return;
+  const float2 rot = make_float2(j.rot_re, j.rot_im);
+  float2 v = make_float2(1.0f, 0.f);
+  auto step = [&]() {
+    v = cmulf(v, rot);
+    const float norm = 1.95f - (v.x * v.x + v.y * v.y);
+    v = make_float2(v.x * norm, v.y * norm);
+  };
+  int i = 0;
+  for (; i + OSC_GATHER <= j.osc_len; i += OSC_GATHER) {
+    float2 e[OSC_GATHER];
+#pragma unroll
+    for (int u = 0; u < OSC_GATHER; u++) {
+      step();
+      e[u] = v;
+    }
+    float4 *dst = reinterpret_cast<float4 *>(j.osc + i);  // hipMalloc'ed table, i % 8 == 0
+#pragma unroll
+    for (int u = 0; u < OSC_GATHER / 2; u++) dst[u] = make_float4(e[2 * u].x, e[2 * u].y, e[2 * u + 1].x, e[2 * u + 1].y);
+  }
+  for (; i < j.osc_len; i++) {
+    step();
+    j.osc[i] = v;
+  }
+}
+
 // ------------------------------------------------------------------ host
-struct Vfo {
+struct Bufs {  // device memory of one VFO: a main VFO's own, a sub-VFO's slot
+  float2 *osc = nullptr;
+  int osc_len = 0;
+  float2 *hist[2] = {nullptr, nullptr};  // [parity][stage][11]
+  float2 *stage[MAX_STAGES] = {};
+  float2 *chain = nullptr;  // output of mix + half-bands
+  float2 *zext = nullptr, *wext = nullptr;
+  float *uext = nullptr, *late_taps = nullptr, *usb_taps = nullptr, *hil = nullptr;
+  int16_t *out16 = nullptr;
+  int8_t *iq = nullptr;
+};
+
+struct Vfo : Bufs {
   bool main = false, active = false, has_subs = false, publish = false;
+  bool iq_out = false;         // main: publishes 4-bit IQ (no [vfos] entry under it at create)
+  bool used = false;           // sub: the id is given out
+  bool skip = false;           // sub: not computed by this process
+  bool start_pending = false;  // sub: start_kernel has not run for it yet
+  bool ran = false;            // sub: out16 holds its audio of the last batch
+  int slot = -1;               // sub: index into aero_chan::slots while it runs
   int parent = -1;
   int fs = 0, k = 0, late = 0, out_rate = 0, filterbw = 0, scalecomp = 1;
   int spb = 0;  // input samples per read
   int S = 0;    // output samples per read
   double mixer = 0;
   float gain = 0;
-  float2 *osc = nullptr;
-  int osc_len = 0;
-  long long nmix = 0;
-  float2 *hist[2] = {nullptr, nullptr};  // [parity][stage][11]
-  float2 *stage[MAX_STAGES] = {};
-  float2 *chain = nullptr;  // output of mix + half-bands
-  float2 *zext = nullptr, *wext = nullptr;
-  float *uext = nullptr, *late_taps = nullptr, *usb_taps = nullptr, *hil = nullptr;
-  int nlate = 0, nusb = 0;
-  int16_t *out16 = nullptr;
-  int8_t *iq = nullptr;
+  int nlate = 0, nusb = 0;  // tap counts (<= 0: no such design)
   std::vector<int16_t> host_out;
   std::vector<int8_t> host_iq;
 };
+
+cslots::Shape shape_of(const Vfo &v) { return {v.parent, v.k, v.late, v.spb, v.S, v.out_rate, v.filterbw}; }
 
 }  // namespace
 
@@ -283,6 +365,17 @@ struct aero_chan {
   char *d_jobs = nullptr, *h_jobs = nullptr;
   size_t jobs_cap = 0;
   float *pin_in = nullptr;
+  // run-time VFOs: subs is indexed by [vfos] id (ids), a running one owns slots[slot]
+  long long reads = 0;  // reads taken so far: every VFO's NCO index is reads * spb
+  cslots::IdAlloc ids;
+  cslots::SlotPool pool;
+  std::vector<Bufs> slots;
+  bool dirty = false;  // VFOs started or stopped since the last start_kernel
+  StartJob *d_start = nullptr, *h_start = nullptr;
+  hipEvent_t ev_start = nullptr;
+  size_t cap_nv = 0;  // VFOs d_jobs / d_start are sized for
+  size_t dev_bytes = 0;
+  uint64_t vfo_inits = 0;
 };
 
 namespace {
@@ -293,6 +386,7 @@ int dalloc(aero_chan *c, T *&p, size_t n) {
   const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
   if (hipMalloc(&q, bytes) != hipSuccess) return AERO_E_NOMEM;
   c->dmem.push_back(q);
+  c->dev_bytes += bytes;
   CHK(hipMemset(q, 0, bytes));
   p = reinterpret_cast<T *>(q);
   return AERO_OK;
@@ -304,53 +398,189 @@ int upload(aero_chan *c, float *&p, const std::vector<float> &v) {
   return AERO_OK;
 }
 
-int vfo_alloc(aero_chan *c, Vfo &v) {
+// the late (1 in 5/6) and audio low-pass designs of a sub-VFO; sets its tap counts
+void design_taps(Vfo &v, std::vector<float> &late_taps, std::vector<float> &usb_taps) {
+  v.nlate = v.nusb = 0;
+  if (v.late) {
+    const int tr = v.out_rate;  // targetRate after the late division (vfo.cpp:71-79)
+    late_taps.assign(4096, 0.f);
+    v.nlate = host_pub_low_pass(2, tr * v.late, tr / 2, (double)tr / (v.late - 1), late_taps.data(), 4096);
+    late_taps.resize(std::max(v.nlate, 0));
+  }
+  if (v.filterbw > 0) {  // vfo.cpp:92-102
+    usb_taps.assign(4096, 0.f);
+    v.nusb = host_pub_low_pass(2, v.out_rate, v.filterbw, (double)v.filterbw / 4, usb_taps.data(), 4096);
+    usb_taps.resize(std::max(v.nusb, 0));
+  }
+}
+
+int stages_alloc(aero_chan *c, const Vfo &v, Bufs &b) {
   const size_t T = (size_t)c->cfg.max_blocks;
-  {
-    std::vector<float> q(2 * (size_t)host_pub_osc_len(v.fs));
-    host_pub_osc(v.fs, v.mixer, q.data());
-    float *qd;
-    if (int rc = upload(c, qd, q)) return rc;
-    v.osc = reinterpret_cast<float2 *>(qd);
-    v.osc_len = (int)(q.size() / 2);
-  }
   for (int p = 0; p < 2; p++)
-    if (int rc = dalloc(c, v.hist[p], (size_t)MAX_STAGES * 11)) return rc;
-  const int Lk = v.spb >> v.k;
-  if (v.main) {
-    if (int rc = dalloc(c, v.chain, T * Lk)) return rc;
-    if (v.publish && !v.has_subs)
-      if (int rc = dalloc(c, v.iq, T * Lk)) return rc;
-  } else {
-    std::vector<float> hil(HIL_LEN);
-    host_pub_hilbert(HIL_LEN, v.S, hil.data());  // FIRHilbert(125, samplesOut) (vfo.cpp:112)
-    if (int rc = upload(c, v.hil, hil)) return rc;
-    if (int rc = dalloc(c, v.wext, HIL_H + T * v.S)) return rc;
-    std::vector<float> taps(4096);
-    if (v.late) {
-      const int tr = v.out_rate;  // targetRate after the late division (vfo.cpp:71-79)
-      v.nlate = host_pub_low_pass(2, tr * v.late, tr / 2, (double)tr / (v.late - 1), taps.data(), 4096);
-      if (v.nlate <= 0 || v.nlate > Lk) return AERO_E_INVALID;
-      taps.resize(v.nlate);
-      if (int rc = upload(c, v.late_taps, taps)) return rc;
-      if (int rc = dalloc(c, v.zext, v.nlate + T * Lk)) return rc;
-      v.chain = v.zext + v.nlate;
-    } else {
-      v.chain = v.wext + HIL_H;
-    }
-    if (v.filterbw > 0) {  // vfo.cpp:92-102
-      taps.assign(4096, 0.f);
-      v.nusb = host_pub_low_pass(2, v.out_rate, v.filterbw, (double)v.filterbw / 4, taps.data(), 4096);
-      if (v.nusb <= 0 || v.nusb > v.S) return AERO_E_INVALID;
-      taps.resize(v.nusb);
-      if (int rc = upload(c, v.usb_taps, taps)) return rc;
-      if (int rc = dalloc(c, v.uext, v.nusb + T * v.S)) return rc;
-    }
-    if (int rc = dalloc(c, v.out16, T * v.S)) return rc;
-  }
+    if (int rc = dalloc(c, b.hist[p], (size_t)MAX_STAGES * 11)) return rc;
   for (int s = 0; s + 1 < v.k; s++)
-    if (int rc = dalloc(c, v.stage[s], T * (size_t)(v.spb >> (s + 1)))) return rc;
-  if (v.k > 0) v.stage[v.k - 1] = v.chain;
+    if (int rc = dalloc(c, b.stage[s], T * (size_t)(v.spb >> (s + 1)))) return rc;
+  if (v.k > 0) b.stage[v.k - 1] = b.chain;
+  return AERO_OK;
+}
+
+// a main VFO's buffers and its NCO table (fixed at create, so from the host)
+int main_alloc(aero_chan *c, Vfo &v) {
+  const size_t T = (size_t)c->cfg.max_blocks;
+  std::vector<float> q(2 * (size_t)host_pub_osc_len(v.fs));
+  host_pub_osc(v.fs, v.mixer, q.data());
+  float *qd;
+  if (int rc = upload(c, qd, q)) return rc;
+  v.osc = reinterpret_cast<float2 *>(qd);
+  v.osc_len = (int)(q.size() / 2);
+  const int Lk = v.spb >> v.k;
+  if (int rc = dalloc(c, v.chain, T * Lk)) return rc;
+  if (v.iq_out)
+    if (int rc = dalloc(c, v.iq, T * Lk)) return rc;
+  return stages_alloc(c, v, v);
+}
+
+// a new slot of v's shape: the buffers, the constant taps and an NCO table
+// that start_kernel fills.  Waits for the device.
+int slot_alloc(aero_chan *c, Vfo &v, Bufs &b) {
+  const size_t T = (size_t)c->cfg.max_blocks;
+  const int Lk = v.spb >> v.k;
+  std::vector<float> late_taps, usb_taps;
+  design_taps(v, late_taps, usb_taps);
+  if (v.late && (v.nlate <= 0 || v.nlate > Lk)) return AERO_E_INVALID;
+  if (v.filterbw > 0 && (v.nusb <= 0 || v.nusb > v.S)) return AERO_E_INVALID;
+  b.osc_len = host_pub_osc_len(v.fs);
+  if (int rc = dalloc(c, b.osc, (size_t)b.osc_len)) return rc;
+  std::vector<float> hil(HIL_LEN);
+  host_pub_hilbert(HIL_LEN, v.S, hil.data());  // FIRHilbert(125, samplesOut) (vfo.cpp:112)
+  if (int rc = upload(c, b.hil, hil)) return rc;
+  if (int rc = dalloc(c, b.wext, HIL_H + T * v.S)) return rc;
+  if (v.late) {
+    if (int rc = upload(c, b.late_taps, late_taps)) return rc;
+    if (int rc = dalloc(c, b.zext, v.nlate + T * Lk)) return rc;
+    b.chain = b.zext + v.nlate;
+  } else {
+    b.chain = b.wext + HIL_H;
+  }
+  if (v.filterbw > 0) {
+    if (int rc = upload(c, b.usb_taps, usb_taps)) return rc;
+    if (int rc = dalloc(c, b.uext, v.nusb + T * v.S)) return rc;
+  }
+  if (int rc = dalloc(c, b.out16, T * v.S)) return rc;
+  if (int rc = stages_alloc(c, v, b)) return rc;
+  CHK(hipDeviceSynchronize());  // the clears above ran on the null stream
+  return AERO_OK;
+}
+
+// d_jobs / d_start for nv VFOs (mains and [vfos] ids and free slots); grows
+// only after the batch that reads the old blobs has completed
+int ensure_cap(aero_chan *c, size_t nv) {
+  if (nv <= c->cap_nv) return AERO_OK;
+  if (c->d_jobs) {
+    CHK(hipEventSynchronize(c->ev_jobs));
+    CHK(hipEventSynchronize(c->ev_start));
+    CHK(hipStreamSynchronize(c->st));
+    c->dev_bytes -= c->jobs_cap + c->cap_nv * sizeof(StartJob);
+    (void)hipFree(c->d_jobs);
+    (void)hipHostFree(c->h_jobs);
+    (void)hipFree(c->d_start);
+    (void)hipHostFree(c->h_start);
+    c->d_jobs = c->h_jobs = nullptr;
+    c->d_start = c->h_start = nullptr;
+    c->jobs_cap = c->cap_nv = 0;
+  }
+  const size_t cap = 16 * 32 + nv * (MAX_STAGES * sizeof(HbJob) + sizeof(MixJob) + sizeof(UsbJob) + sizeof(IqJob) +
+                                     3 * sizeof(ShiftJob) + 16 * 16);
+  if (hipMalloc(&c->d_jobs, cap) != hipSuccess) return AERO_E_NOMEM;
+  if (hipHostMalloc(&c->h_jobs, cap) != hipSuccess) return AERO_E_NOMEM;
+  if (hipMalloc(&c->d_start, nv * sizeof(StartJob)) != hipSuccess) return AERO_E_NOMEM;
+  if (hipHostMalloc(&c->h_start, nv * sizeof(StartJob)) != hipSuccess) return AERO_E_NOMEM;
+  c->jobs_cap = cap;
+  c->cap_nv = nv;
+  c->dev_bytes += cap + nv * sizeof(StartJob);
+  return AERO_OK;
+}
+
+size_t cap_needed(const aero_chan *c, int extra_ids) {
+  return c->mains.size() + (size_t)(c->ids.count() + extra_ids) + c->pool.free_count() + 1;
+}
+
+// gives running sub-VFO `id` a slot of its shape (a free one, else a new
+// one) and queues its start
+int start_vfo(aero_chan *c, int id) {
+  Vfo &v = c->subs[id];
+  const cslots::Shape sh = shape_of(v);
+  int slot = c->pool.take(sh);
+  if (slot < 0) {
+    Bufs b;
+    if (int rc = slot_alloc(c, v, b)) return rc;
+    slot = (int)c->slots.size();
+    c->slots.push_back(b);
+  }
+  static_cast<Bufs &>(v) = c->slots[slot];
+  v.slot = slot;
+  v.active = v.start_pending = true;
+  c->dirty = true;
+  return AERO_OK;
+}
+
+void stop_vfo(aero_chan *c, int id) {
+  Vfo &v = c->subs[id];
+  if (v.slot < 0) return;
+  c->pool.put(shape_of(v), v.slot);
+  static_cast<Bufs &>(v) = Bufs{};
+  v.slot = -1;
+  v.active = v.start_pending = v.ran = false;
+  c->dirty = true;
+}
+
+// Before the first read after VFOs started or stopped: a main VFO runs while
+// it publishes IQ or has a running sub-VFO, one that runs again gets zero
+// half-band history, and every started sub-VFO zero histories and its NCO
+// table, all in one start_kernel launch.
+int prepare(aero_chan *c) {
+  if (!c->dirty) return AERO_OK;
+  c->dirty = false;
+  std::vector<StartJob> jobs;
+  for (auto &s : c->subs) {
+    if (!s.active || !s.start_pending) continue;
+    s.start_pending = false;
+    StartJob j{};
+    j.osc = s.osc;
+    j.osc_len = s.osc_len;
+    host_pub_osc_rotation(s.fs, s.mixer, &j.rot_re, &j.rot_im);
+    j.hist0 = s.hist[0];
+    j.hist1 = s.hist[1];
+    j.zext = s.zext;
+    j.nlate = s.nlate;
+    j.wext = s.wext;
+    j.uext = s.uext;
+    j.nusb = s.nusb;
+    jobs.push_back(j);
+  }
+  for (size_t m = 0; m < c->mains.size(); m++) {
+    Vfo &mv = c->mains[m];
+    bool want = mv.iq_out;
+    for (auto &s : c->subs) want |= s.active && s.parent == (int)m;
+    if (want && !mv.active) {
+      StartJob j{};
+      j.hist0 = mv.hist[0];
+      j.hist1 = mv.hist[1];
+      jobs.push_back(j);
+    }
+    mv.active = want;
+  }
+  if (jobs.empty()) return AERO_OK;
+  if (jobs.size() > c->cap_nv) return AERO_E_INVALID;  // sized by ensure_cap
+  CHK(hipEventSynchronize(c->ev_start));
+  memcpy(c->h_start, jobs.data(), jobs.size() * sizeof(StartJob));
+  CHK(hipMemcpyAsync(c->d_start, c->h_start, jobs.size() * sizeof(StartJob), hipMemcpyHostToDevice, c->st));
+  const int nj = (int)jobs.size();
+  hipLaunchKernelGGL(start_kernel, dim3((nj + START_VFOS - 1) / START_VFOS), dim3(START_LANES), 0, c->st, c->d_start,
+                     nj);
+  CHK(hipGetLastError());
+  CHK(hipEventRecord(c->ev_start, c->st));
+  c->vfo_inits++;
   return AERO_OK;
 }
 
@@ -375,8 +605,9 @@ int run_impl(aero_chan *c) {
   std::vector<IqJob> iq;
   std::vector<ShiftJob> sh;
   auto chain_jobs = [&](Vfo &v, const float2 *in, int side) {
+    const long long nmix = c->reads * v.spb;  // NCO ticks of the reads taken, whenever the VFO started
     if (v.k == 0) {
-      mix[side].push_back({in, v.chain, v.osc, v.nmix, (long long)nb * v.spb, v.osc_len});
+      mix[side].push_back({in, v.chain, v.osc, nmix, (long long)nb * v.spb, v.osc_len});
       return;
     }
     for (int s = 0; s < v.k; s++) {
@@ -386,7 +617,7 @@ int run_impl(aero_chan *c) {
       j.hist = v.hist[p] + s * 11;
       j.hist_out = v.hist[p ^ 1] + s * 11;
       j.osc = s == 0 ? v.osc : nullptr;
-      j.n0 = v.nmix;
+      j.n0 = nmix;
       j.osc_len = v.osc_len;
       j.L = v.spb >> s;
       hb[side][s].push_back(j);
@@ -499,10 +730,8 @@ int run_impl(aero_chan *c) {
     hipLaunchKernelGGL(shift_kernel, dim3(1, (unsigned)sh.size()), dim3(256), 0, c->st,
                        reinterpret_cast<const ShiftJob *>(dptr(k)));
   CHK(hipGetLastError());
-  for (auto &m : c->mains)
-    if (m.active) m.nmix += (long long)nb * m.spb;
-  for (auto &s : c->subs)
-    if (s.active) s.nmix += (long long)nb * s.spb;
+  for (auto &s : c->subs) s.ran = s.active;
+  c->reads += nb;
   c->parity ^= 1;
   c->last_nblk = nb;
   c->pending = 0;
@@ -538,13 +767,79 @@ void destroy_impl(aero_chan *c) {
   for (void *p : c->dmem) (void)hipFree(p);
   if (c->d_jobs) (void)hipFree(c->d_jobs);
   if (c->h_jobs) (void)hipHostFree(c->h_jobs);
+  if (c->d_start) (void)hipFree(c->d_start);
+  if (c->h_start) (void)hipHostFree(c->h_start);
   if (c->pin_in) (void)hipHostFree(c->pin_in);
+  if (c->ev_start) (void)hipEventDestroy(c->ev_start);
   if (c->ev_jobs) (void)hipEventDestroy(c->ev_jobs);
   if (c->ev_pin) (void)hipEventDestroy(c->ev_pin);
   if (c->ev_in) (void)hipEventDestroy(c->ev_in);
   if (c->ev_out) (void)hipEventDestroy(c->ev_out);
   if (c->st) (void)hipStreamDestroy(c->st);
 }
+
+// one [vfos] entry against the main VFOs (publisher.cpp:151-222)
+int resolve_sub(const aero_chan *c, const aero_chan_vfo &s, Vfo &v) {
+  const aero_chan_cfg *cfg = &c->cfg;
+  const int Fs = cfg->sample_rate, nmain = (int)c->mains.size();
+  const int vfo_freq = s.frequency + cfg->mix_offset;
+  int out_rate = s.out_rate;
+  if (out_rate == 0 && s.data_rate > 0) out_rate = s.data_rate == 600 ? 12000 : (s.data_rate == 1200 ? 24000 : 48000);
+  if (out_rate <= 0) return AERO_E_INVALID;
+  int main_vfo_freq = 0, main_out = Fs, main_idx = -1;
+  for (int a = 0; a < nmain; a++) {
+    const int diff = (int)std::fabs((cfg->center_frequency - c->mains[a].mixer) - vfo_freq);
+    if (diff < c->mains[a].out_rate) {
+      main_idx = a;
+      main_vfo_freq = (int)c->mains[a].mixer;
+      main_out = c->mains[a].out_rate;
+      break;
+    }
+  }
+  if (main_idx < 0 && nmain > 0) return AERO_E_INVALID;  // would be fed another main VFO's stream
+  int late = 0, k;
+  if ((main_out / 48000) == 5) {
+    k = int(log2(main_out / (5 * out_rate)));
+    late = 5;
+  } else if ((main_out / 48000) == 6) {
+    k = int(log2(main_out / (6 * out_rate)));
+    late = 6;
+  } else {
+    k = int(log2(Fs / out_rate)) - int(log2(Fs / main_out));
+  }
+  if (k < 0 || k > MAX_STAGES) return AERO_E_INVALID;
+  v.k = k;
+  v.late = late;
+  v.filterbw = s.filter_bandwidth;
+  v.gain = (float)s.gain / 100;
+  v.mixer = (cfg->center_frequency - main_vfo_freq) - vfo_freq;
+  v.fs = main_out;
+  v.parent = main_idx;
+  v.spb = main_out / c->bufsplit;
+  int targetRate = (int)(v.fs / (pow(2, k)));
+  int so = (int)(v.spb / (pow(2, k)));
+  if (late) {
+    targetRate = targetRate / late;
+    so = so / late;
+  }
+  v.out_rate = targetRate;
+  v.S = so;
+  v.skip = s.skip != 0;
+  if (main_idx >= 0) {
+    const Vfo &m = c->mains[main_idx];
+    // the sub-VFO's read is exactly its main VFO's output read (vfo.cpp:122-126, 154-160)
+    if (v.spb != m.S || !chain_ok(v.spb, k)) return AERO_E_INVALID;
+    const int Lk = v.spb >> k;
+    if (late && (Lk % late || Lk / late != so)) return AERO_E_INVALID;
+    if (so < HIL_H) return AERO_E_INVALID;
+    std::vector<float> lt, ut;
+    design_taps(v, lt, ut);  // the counts, for aero_chan_vfo_settle
+  }
+  return AERO_OK;
+}
+
+// [vfos] id in use
+bool vfo_ok(const aero_chan *c, int v) { return c && c->ids.in_use(v); }
 
 }  // namespace
 
@@ -590,84 +885,32 @@ int aero_chan_create(const aero_chan_cfg *cfg, const aero_chan_main *mains, int 
     if (v.k > MAX_STAGES || !chain_ok(v.spb, v.k)) return AERO_E_INVALID;
     c->mains.push_back(v);
   }
-  for (int i = 0; i < nvfo; i++) {  // publisher.cpp:151-222
-    const aero_chan_vfo &s = vfos[i];
+  for (int i = 0; i < nvfo; i++) {
     Vfo v;
-    const int vfo_freq = s.frequency + cfg->mix_offset;
-    int out_rate = s.out_rate;
-    if (out_rate == 0 && s.data_rate > 0) out_rate = s.data_rate == 600 ? 12000 : (s.data_rate == 1200 ? 24000 : 48000);
-    if (out_rate <= 0) return AERO_E_INVALID;
-    int main_vfo_freq = 0, main_out = Fs, main_idx = -1;
-    for (int a = 0; a < nmain; a++) {
-      const int diff = (int)std::fabs((cfg->center_frequency - c->mains[a].mixer) - vfo_freq);
-      if (diff < c->mains[a].out_rate) {
-        main_idx = a;
-        main_vfo_freq = (int)c->mains[a].mixer;
-        main_out = c->mains[a].out_rate;
-        break;
-      }
-    }
-    if (main_idx < 0 && nmain > 0) return AERO_E_INVALID;  // would be fed another main VFO's stream
-    int late = 0, k;
-    if ((main_out / 48000) == 5) {
-      k = int(log2(main_out / (5 * out_rate)));
-      late = 5;
-    } else if ((main_out / 48000) == 6) {
-      k = int(log2(main_out / (6 * out_rate)));
-      late = 6;
-    } else {
-      k = int(log2(Fs / out_rate)) - int(log2(Fs / main_out));
-    }
-    if (k < 0 || k > MAX_STAGES) return AERO_E_INVALID;
-    v.k = k;
-    v.late = late;
-    v.filterbw = s.filter_bandwidth;
-    v.gain = (float)s.gain / 100;
-    v.mixer = (cfg->center_frequency - main_vfo_freq) - vfo_freq;
-    v.fs = main_out;
-    v.parent = main_idx;
-    v.spb = main_out / c->bufsplit;
-    int targetRate = (int)(v.fs / (pow(2, k)));
-    int so = (int)(v.spb / (pow(2, k)));
-    if (late) {
-      targetRate = targetRate / late;
-      so = so / late;
-    }
-    v.out_rate = targetRate;
-    v.S = so;
-    v.active = main_idx >= 0 && !s.skip;
-    if (main_idx >= 0) {
-      Vfo &m = c->mains[main_idx];
-      m.has_subs = true;
-      // the sub-VFO's read is exactly its main VFO's output read (vfo.cpp:122-126, 154-160)
-      if (v.spb != m.S || !chain_ok(v.spb, k)) return AERO_E_INVALID;
-      const int Lk = v.spb >> k;
-      if (late && (Lk % late || Lk / late != so)) return AERO_E_INVALID;
-      if (so < HIL_H) return AERO_E_INVALID;
-    }
+    if (int rc = resolve_sub(c.get(), vfos[i], v)) return rc;
+    if (v.parent >= 0) c->mains[v.parent].has_subs = true;
+    v.used = true;
+    c->ids.take();  // ids 0 .. nvfo-1
     c->subs.push_back(v);
   }
-  for (auto &m : c->mains) m.active = m.publish && !m.has_subs;
+  for (auto &m : c->mains) m.active = m.iq_out = m.publish && !m.has_subs;
   for (auto &s : c->subs)
-    if (s.active) c->mains[s.parent].active = true;
+    if (s.parent >= 0 && !s.skip) c->mains[s.parent].active = true;
   CHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+  CHK(hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming));
   CHK(hipEventCreateWithFlags(&c->ev_jobs, hipEventDisableTiming));
   CHK(hipEventCreateWithFlags(&c->ev_pin, hipEventDisableTiming));
   CHK(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
   CHK(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
   if (int rc = dalloc(c.get(), c->in, (size_t)cfg->max_blocks * c->B)) return rc;
   if (int rc = dalloc(c.get(), c->avept, 1)) return rc;
+  // every main VFO, running or not: a [vfos] entry may be opened under it later
   for (auto &m : c->mains)
-    if (m.active)
-      if (int rc = vfo_alloc(c.get(), m)) return rc;
-  for (auto &s : c->subs)
-    if (s.active)
-      if (int rc = vfo_alloc(c.get(), s)) return rc;
-  const size_t nv = c->mains.size() + c->subs.size() + 1;
-  c->jobs_cap = 16 * 32 + nv * (MAX_STAGES * sizeof(HbJob) + sizeof(MixJob) + sizeof(UsbJob) + sizeof(IqJob) +
-                                3 * sizeof(ShiftJob) + 16 * 16);
-  if (hipMalloc(&c->d_jobs, c->jobs_cap) != hipSuccess) return AERO_E_NOMEM;
-  if (hipHostMalloc(&c->h_jobs, c->jobs_cap) != hipSuccess) return AERO_E_NOMEM;
+    if (int rc = main_alloc(c.get(), m)) return rc;
+  for (int i = 0; i < nvfo; i++)
+    if (c->subs[i].parent >= 0 && !c->subs[i].skip)
+      if (int rc = start_vfo(c.get(), i)) return rc;
+  if (int rc = ensure_cap(c.get(), cap_needed(c.get(), 0))) return rc;
   CHK(hipDeviceSynchronize());
   *out = c.release();
   return AERO_OK;
@@ -687,7 +930,7 @@ int aero_chan_block_len(aero_chan *c, int *block_len) {
 }
 
 int aero_chan_vfo_info(aero_chan *c, int v, int *info) {
-  if (!c || !info || v < 0 || v >= (int)c->subs.size()) return AERO_E_INVALID;
+  if (!info || !vfo_ok(c, v)) return AERO_E_INVALID;
   const Vfo &s = c->subs[v];
   info[0] = s.parent;
   info[1] = s.out_rate;
@@ -717,6 +960,8 @@ int aero_chan_push(aero_chan *c, const float *iq, size_t nblocks, int dev) {
     return AERO_E_FULL;
   if (dev && nblocks)
     if (int rc = check_dev_ptr(iq)) return rc;
+  if (nblocks)
+    if (int rc = prepare(c)) return rc;
   size_t done = 0;
   while (done < nblocks) {
     if (c->pending == c->cfg.max_blocks)
@@ -750,6 +995,7 @@ int aero_chan_push(aero_chan *c, const float *iq, size_t nblocks, int dev) {
 int aero_chan_run(aero_chan *c) {
   if (!c) return AERO_E_INVALID;
   CHK(hipSetDevice(c->cfg.device));
+  if (int rc = prepare(c)) return rc;
   return run_impl(c);
 }
 
@@ -761,15 +1007,15 @@ int aero_chan_sync(aero_chan *c) {
 }
 
 int aero_chan_vfo_output(aero_chan *c, int v, const int16_t **dptr, size_t *n) {
-  if (!c || !dptr || !n || v < 0 || v >= (int)c->subs.size()) return AERO_E_INVALID;
+  if (!dptr || !n || !vfo_ok(c, v)) return AERO_E_INVALID;
   const Vfo &s = c->subs[v];
   *dptr = s.out16;
-  *n = s.active ? (size_t)c->last_nblk * s.S : 0;
+  *n = s.ran ? (size_t)c->last_nblk * s.S : 0;
   return AERO_OK;
 }
 
 int aero_chan_pop_audio(aero_chan *c, int v, int16_t *dst, size_t cap, size_t *n) {
-  if (!c || v < 0 || v >= (int)c->subs.size()) return AERO_E_INVALID;
+  if (!vfo_ok(c, v)) return AERO_E_INVALID;
   return pop_vec(c->subs[v].host_out, dst, cap, n);
 }
 
@@ -787,9 +1033,9 @@ int aero_chan_feed(aero_chan *c, aero_engine *e, const int *ch) {
   std::vector<const int16_t *> src;
   std::vector<size_t> n;
   std::vector<uint32_t> fs;
-  for (size_t v = 0; v < c->subs.size(); v++) {
+  for (int v = 0; v < c->ids.count(); v++) {  // closed ids are not running
     const Vfo &s = c->subs[v];
-    if (ch[v] < 0 || !s.active || !c->last_nblk) continue;
+    if (ch[v] < 0 || !s.ran || !c->last_nblk) continue;
     chs.push_back(ch[v]);
     src.push_back(s.out16);
     n.push_back((size_t)c->last_nblk * s.S);
@@ -798,6 +1044,100 @@ int aero_chan_feed(aero_chan *c, aero_engine *e, const int *ch) {
   if (chs.empty()) return AERO_OK;
   CHK(hipEventRecord(c->ev_out, c->st));
   return aero_engine_feed_dev(e, (int)chs.size(), chs.data(), src.data(), n.data(), fs.data(), c->ev_out, c->st);
+}
+
+int aero_chan_vfo_open(aero_chan *c, const aero_chan_vfo *cfg, int *v_out) {
+  if (!c || !cfg || !v_out) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  Vfo v;
+  if (int rc = resolve_sub(c, *cfg, v)) return rc;
+  // no main VFO covers it, or the one that does publishes its own stream as
+  // IQ (a sub-VFO under it would silence that, vfo.cpp:176-185)
+  if (v.parent < 0 || c->mains[v.parent].iq_out) return AERO_E_INVALID;
+  if (int rc = run_impl(c)) return rc;  // the reads taken so far run without it
+  const int id = c->ids.take();
+  if (id >= (int)c->subs.size()) c->subs.resize((size_t)id + 1);
+  v.used = true;
+  c->subs[id] = v;
+  int rc = v.skip ? AERO_OK : start_vfo(c, id);
+  if (!rc) rc = ensure_cap(c, cap_needed(c, 0));  // a slot that was free is now this id's: no growth
+  if (rc) {
+    stop_vfo(c, id);
+    c->subs[id] = Vfo();
+    c->ids.release(id);
+    return rc;
+  }
+  *v_out = id;
+  return AERO_OK;
+}
+
+int aero_chan_vfo_close(aero_chan *c, int v) {
+  if (!vfo_ok(c, v)) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  if (int rc = run_impl(c)) return rc;  // the reads taken so far run with it
+  stop_vfo(c, v);
+  c->subs[v] = Vfo();
+  c->ids.release(v);
+  return AERO_OK;
+}
+
+int aero_chan_vfo_skip(aero_chan *c, int v, int skip) {
+  if (!vfo_ok(c, v)) return AERO_E_INVALID;
+  Vfo &s = c->subs[v];
+  if (s.parent < 0) return skip ? AERO_OK : AERO_E_INVALID;  // never runs (no main VFOs)
+  if (s.skip == (skip != 0)) return AERO_OK;
+  CHK(hipSetDevice(c->cfg.device));
+  if (int rc = run_impl(c)) return rc;
+  if (skip) {
+    stop_vfo(c, v);
+  } else {
+    if (int rc = ensure_cap(c, cap_needed(c, 0))) return rc;
+    if (int rc = start_vfo(c, v)) return rc;
+  }
+  s.skip = skip != 0;
+  return AERO_OK;
+}
+
+int aero_chan_reserve(aero_chan *c, const aero_chan_vfo *like, int n) {
+  if (!c || !like || n < 1) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  Vfo v;
+  if (int rc = resolve_sub(c, *like, v)) return rc;
+  if (v.parent < 0 || c->mains[v.parent].iq_out) return AERO_E_INVALID;
+  for (int i = 0; i < n; i++) {
+    Bufs b;
+    if (int rc = slot_alloc(c, v, b)) return rc;
+    c->slots.push_back(b);
+    c->pool.put(shape_of(v), (int)c->slots.size() - 1);
+  }
+  return ensure_cap(c, cap_needed(c, 0));
+}
+
+int aero_chan_vfo_count(aero_chan *c, int *n) {
+  if (!c || !n) return AERO_E_INVALID;
+  *n = c->ids.count();
+  return AERO_OK;
+}
+
+int aero_chan_vfo_settle(aero_chan *c, int v, size_t *samples) {
+  if (!samples || !vfo_ok(c, v)) return AERO_E_INVALID;
+  const Vfo &s = c->subs[v];
+  if (s.parent < 0) return AERO_E_INVALID;
+  *samples = cslots::settle(std::max(s.nusb, 0), std::max(s.nlate, 0), s.late, s.k, c->mains[s.parent].k);
+  return AERO_OK;
+}
+
+int aero_chan_stat(aero_chan *c, const char *name, uint64_t *value) {
+  if (!c || !name || !value) return AERO_E_INVALID;
+  if (!strcmp(name, "device_bytes"))
+    *value = c->dev_bytes;
+  else if (!strcmp(name, "vfo_inits"))
+    *value = c->vfo_inits;
+  else if (!strcmp(name, "slots_free"))
+    *value = c->pool.free_count();
+  else
+    return AERO_E_INVALID;
+  return AERO_OK;
 }
 
 }  // extern "C"

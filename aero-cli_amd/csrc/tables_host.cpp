@@ -229,10 +229,17 @@ int host_pub_osc_len(double sampleRate) { return (int)sampleRate; }
 
 // Oscillator::Oscillator (publish/oscillator.cpp:4-28): queue[i] is the
 // rotator after i+1 renormalised steps, in std::complex<float> as there
+void host_pub_osc_rotation(double sampleRate, double frequency, float *re, float *im) {
+  const double anglePerSample = 2.0 * M_PI * frequency / sampleRate;
+  *re = (float)cos(anglePerSample);
+  *im = (float)sin(anglePerSample);
+}
+
 void host_pub_osc(double sampleRate, double frequency, float *queue) {
   typedef std::complex<float> cpxf;
-  const double anglePerSample = 2.0 * M_PI * frequency / sampleRate;
-  const cpxf rotation((float)cos(anglePerSample), (float)sin(anglePerSample));
+  float rre, rim;
+  host_pub_osc_rotation(sampleRate, frequency, &rre, &rim);
+  const cpxf rotation(rre, rim);
   cpxf v(1.0f, 0);
   const int length = (int)sampleRate;
   for (int i = 0; i < length; i++) {

@@ -31,6 +31,8 @@ void host_hilbert_kernel(double *k);                    // [8192][2]
 // publish/dsp.cpp:181-215, publish/firfilter.cpp:47-99): FP32 as there
 int host_pub_osc_len(double sampleRate);
 void host_pub_osc(double sampleRate, double frequency, float *queue);  // [(int)sampleRate][2]
+// the per-sample rotation host_pub_osc multiplies by (the device fill's input)
+void host_pub_osc_rotation(double sampleRate, double frequency, float *re, float *im);
 void host_pub_hilbert(int len, int Fs, float *points);                 // [len]
 int host_pub_low_pass(double gain, double fs, double cutoff, double tw, float *taps, int cap);
 

@@ -99,6 +99,63 @@ int aero_chan_pop_iq(aero_chan *c, int m, int8_t *dst, size_t cap, size_t *n);
  * (aero_push_pcm_dev).  Call once per aero_chan_run. */
 int aero_chan_feed(aero_chan *c, aero_engine *e, const int *ch);
 
+/*
+ * [vfos] entries while the receiver runs.
+ *
+ * Every stage of a VFO has finite memory and its NCO is indexed by the reads
+ * the channeliser has taken, so a VFO that starts at read k with zero filter
+ * histories produces, after aero_chan_vfo_settle output samples, bit for bit
+ * the audio of a VFO that was there from read 0, and from its first sample
+ * the audio of such a VFO whose input was silent until read k.  A VFO's
+ * output does not depend on when it was opened, and no other VFO's audio and
+ * no main VFO's IQ changes by one bit when one comes or goes.
+ *
+ * The ids of aero_chan_create's entries are 0 .. nvfo-1.  A VFO that is
+ * closed or skipped gives its device slot to a free list of its shape (main
+ * VFO, half-band stages, late decimation, samples per read, output rate and
+ * audio filter, which fix the tap counts); a VFO that starts takes the free
+ * slot of its shape with the smallest index.  Where there is none it
+ * allocates one, which waits for the device; aero_chan_reserve avoids that.
+ * The starts since the last read share one kernel launch at the next
+ * aero_chan_push / aero_chan_run, which clears their histories and fills
+ * their NCO tables on the device.
+ *
+ * aero_chan_vfo_open, _close and _skip first run the reads that are pushed
+ * and not yet run, as aero_chan_run does (without the opened VFO, with the
+ * closed one): call them after aero_chan_feed / aero_chan_vfo_output have
+ * used the previous batch.
+ */
+/* Adds one [vfos] entry, resolved as aero_chan_create resolves them (the
+ * same AERO_E_INVALID cases; also when no main VFO covers the frequency, or
+ * the one that does publishes 4-bit IQ, which a sub-VFO would silence).
+ * *v_out: the smallest free id.  The VFO takes part from the first read
+ * pushed after the call; before the first read at all it is exactly an entry
+ * given to aero_chan_create.  cfg->skip: the id is taken, nothing runs. */
+int aero_chan_vfo_open(aero_chan *c, const aero_chan_vfo *cfg, int *v_out);
+/* Audio of v that has not been popped is dropped.  Afterwards every call
+ * that takes v returns AERO_E_INVALID and aero_chan_feed ignores ch[v], until
+ * the id is given out again. */
+int aero_chan_vfo_close(aero_chan *c, int v);
+/* The skip flag of entry v (from create or open) at run time: the id and the
+ * configuration stay; skip = 1 releases the slot as close does (audio that is
+ * not popped stays), skip = 0 starts the VFO as open does.  To hand a VFO to
+ * another process, the receiver clears its skip one read before the owner
+ * sets its own: the receiver's audio from its second read on continues the
+ * owner's when the settle time is below one read. */
+int aero_chan_vfo_skip(aero_chan *c, int v, int skip);
+/* n free slots of the shape `like` resolves to (and room in the job blobs),
+ * so that opens of that shape allocate nothing */
+int aero_chan_reserve(aero_chan *c, const aero_chan_vfo *like, int n);
+/* one past the largest id in use: the length of aero_chan_feed's ch array */
+int aero_chan_vfo_count(aero_chan *c, int *n);
+/* output samples after a start within which v may differ from a VFO that was
+ * always there: 124 (Hilbert) + audio taps + ceil(late taps / late) + 12 per
+ * half-band stage of the VFO and of its main VFO */
+int aero_chan_vfo_settle(aero_chan *c, int v, size_t *samples);
+/* "device_bytes": device memory held; "vfo_inits": start-kernel launches;
+ * "slots_free": free slots held.  Other names: AERO_E_INVALID. */
+int aero_chan_stat(aero_chan *c, const char *name, uint64_t *value);
+
 #ifdef __cplusplus
 }
 #endif
