@@ -130,6 +130,17 @@ def build_schedsim():
     return SCHEDSIM_SO
 
 
+LDSSIM_SO = os.path.join(ROOT, 'tools', 'libcoarse_lds_sim.so')
+
+
+def build_ldssim():
+    """Test-only host view of the coarse kernel's LDS map (tests/test_coarse_lds_map.py)."""
+    src = os.path.join(ROOT, 'tools', 'coarse_lds_sim.cpp')
+    if _stale(LDSSIM_SO, [src, os.path.join(CSRC, 'coarse_lds.h')]):
+        _run(['g++', '-O2', '-std=c++17', '-Wall', '-fPIC', '-shared', '-o', LDSSIM_SO, src])
+    return LDSSIM_SO
+
+
 CHANSLOTS_SO = os.path.join(ROOT, 'tools', 'libchan_slots_sim.so')
 
 
@@ -267,6 +278,7 @@ def build_all(jobs=4):
     build_mathhost()
     build_fftsim()
     build_schedsim()
+    build_ldssim()
     build_chanslots()
     build_hostcheck()
     so = build_engine(jobs)

@@ -860,8 +860,9 @@ AERO_HD double aero_atan2_bf(double y, double x, const double (*cij)[7]) {
 /* --------------------------------------------------------------- log
  * glibc 2.35 __log_fma (sysdeps/ieee754/dbl-64/e_log.c built with -mfma
  * -mavx2: r = fma(z, invc, -1) and GCC's contractions, read from its
- * disassembly), the ifunc target the log10 wrapper calls on FMA hosts. */
-AERO_HD double aero_log(double x) {
+ * disassembly), the ifunc target the log10 wrapper calls on FMA hosts.
+ * tab: aero_g_log_tab or a copy of it (a kernel may keep one in LDS). */
+AERO_HD double aero_log_tab(double x, const double *tab) {
   const uint64_t ix = d2u(x);
   const uint32_t top = (uint32_t)(ix >> 48);
   if (ix - 0x3fee000000000000ULL < 0x3090000000000ULL) {  // |x - 1| < 0x1p-4 (LO..HI)
@@ -890,7 +891,7 @@ AERO_HD double aero_log(double x) {
   const int i = (int)((tmp >> 45) & 127);
   const int k = (int)((int64_t)tmp >> 52);
   const double z = u2d(jx - (tmp & (0xfffULL << 52)));
-  const double invc = aero_g_log_tab[i][0], logc = aero_g_log_tab[i][1];
+  const double invc = tab[2 * i], logc = tab[2 * i + 1];
   const double r = fma(z, invc, -1.0);
   const double kd = (double)k;
   const double w = fma(kd, AERO_G_LN2HI, logc);
@@ -902,8 +903,10 @@ AERO_HD double aero_log(double x) {
   return fma(r * r2, q, fma(r2, A[0], lo)) + hi;
 }
 
+AERO_HD double aero_log(double x) { return aero_log_tab(x, &aero_g_log_tab[0][0]); }
+
 /* log10 (e_log10.c, __log10_finite: SSE2, no fusion) around __log_fma */
-AERO_HD double aero_log10(double x) {
+AERO_HD double aero_log10_tab(double x, const double *tab) {
   const double two54 = 0x1p54;
   int64_t ix = (int64_t)d2u(x);
   int64_t k;
@@ -921,8 +924,9 @@ AERO_HD double aero_log10(double x) {
   const int64_t i = (int64_t)((uint64_t)k >> 63);
   const double y = (double)(k + i);
   x = u2d((uint64_t)(ix & 0x000fffffffffffffLL) | ((uint64_t)(0x3ff - i) << 52));
-  const double z = y * AERO_G_LOG10_2LO + aero_log(x) * AERO_G_IVLN10;
+  const double z = y * AERO_G_LOG10_2LO + aero_log_tab(x, tab) * AERO_G_IVLN10;
   return z + y * AERO_G_LOG10_2HI;
 }
+AERO_HD double aero_log10(double x) { return aero_log10_tab(x, &aero_g_log_tab[0][0]); }
 
 }  // namespace aero

@@ -11,6 +11,8 @@
  * launch is persistent: at most one workgroup per CU, each walking through
  * its share of the channels (coarse_sched.h) with the next channel's state
  * and this channel's hop-control state loaded under the tail's arithmetic,
+ * the next due channel's head (ring image, table gathers) run under this
+ * channel's tail ("the overlapped head" below; coarse_lds.h),
  * and the other waves starting the next channel while lane 0 finishes the
  * hop control.  The 8192-point MSK kinds run several workgroups per CU and
  * keep one workgroup per channel (the same code, a walk of one).
@@ -28,6 +30,7 @@
 #include <type_traits>
 
 #include "aero_math.h"
+#include "coarse_lds.h"
 #include "coarse_sched.h"
 #include "engine_common.h"
 #include "fft_chain.h"
@@ -38,10 +41,12 @@ namespace aero {
 #define CO_HYPOT ::hypot
 #define CO_HYPOT_NR ::hypot
 #define CO_LOG10 ::log10
+#define CO_LOG10_TAB(x, tab) ::log10(x)
 #else
 #define CO_HYPOT aero_hypot
 #define CO_HYPOT_NR aero_hypot_nr
 #define CO_LOG10 aero_log10
+#define CO_LOG10_TAB(x, tab) aero_log10_tab(x, tab)
 #endif
 
 // Geometry of one channel's coarse estimate (decode/coarsefreqestimate.cpp:39-76
@@ -52,7 +57,7 @@ struct CoarseK;
 template <>
 struct CoarseK<MODE_OQPSK> {
   static constexpr int LOG2N = 14, HOPN = 4096, START = 3584, STOP = 12800, ILO = 4608, IHI = 11776, EPB = 1792;
-  static constexpr int YLO = 2815, YHI = 13568;
+  static constexpr int YLO = clds::YLO14, YHI = clds::YHI14;
   static constexpr double FS = 48000.0;
 };
 // the C channel: setSettings(14, 10500, 8400, 48000): the OQPSK bins, the
@@ -61,7 +66,7 @@ struct CoarseK<MODE_OQPSK> {
 template <>
 struct CoarseK<MODE_C8400> {
   static constexpr int LOG2N = 14, HOPN = 4096, START = 3584, STOP = 12800, ILO = 4608, IHI = 11776, EPB = 1434;
-  static constexpr int YLO = 2815, YHI = 13568;
+  static constexpr int YLO = clds::YLO14, YHI = clds::YHI14;
   static constexpr double FS = 48000.0;
 };
 // MSK at Fs (setSettings(13, 900, 600, Fs)): hzperbin = Fs / 8192; startbin
@@ -232,7 +237,10 @@ __device__ __forceinline__ bool hop_control(HopCtl &h, std::integral_constant<in
 // smoothing, fold search, lane 0's hop control; slots 0-9), wave 0's whole
 // time in the kernel over the workgroups that ran a hop (slot 10: less the
 // sections, the turnover between channels and the launch) and the number of
-// hops (slot 11)
+// hops (slot 11).  With the overlapped head slots 0 and 1 count the plain
+// heads only and slot 2 the successor's mix; its ring words and image stores
+// run inside slot 6, its table gathers inside slot 7, the twiddle write and
+// the y stores inside slot 8 (scripts/coarse_stamps.py)
 constexpr int CSTAMP_N = 12;
 #ifdef AERO_X_STAMPS
 __device__ unsigned long long g_cstamps[CSTAMP_N];
@@ -305,17 +313,54 @@ __device__ __forceinline__ HopEpi load_epi(const DevState &S, int C, int c) {
   return e;
 }
 
-template <int M>
+// The workgroup's LDS (coarse_lds.h).  Without the overlapped head: the four
+// arrays as they always were.  With it: one raw buffer carved at the map's
+// offsets, because the next channel's ring image lies across the end of lds,
+// s_tw and the spare behind it.
+template <int L, int YLEN, bool OVL>
+struct CoarseLds {
+  double *lds;
+  double2 *s_tw;
+  double *red_v;
+  int *red_i;
+  uint32_t *img;   // the overlapped head's ring image (OVL only)
+  double *logtab;  // its copy of aero_g_log_tab (OVL only)
+};
+template <int L, int YLEN, bool OVL>
+__device__ __forceinline__ CoarseLds<L, YLEN, OVL> coarse_lds() {
+  using LM = clds::Map<L, YLEN, OVL>;
+  static_assert(LM::TWLEN == TwLds<L>::LEN && clds::ypad(12345) == fftl::ypadn<6>(12345), "coarse_lds.h restates these");
+  if constexpr (OVL) {
+    __shared__ __attribute__((aligned(16))) unsigned char raw[LM::TOTAL];
+    return {reinterpret_cast<double *>(raw + LM::LDS_OFF), reinterpret_cast<double2 *>(raw + LM::TW_OFF),
+            reinterpret_cast<double *>(raw + LM::REDV_OFF), reinterpret_cast<int *>(raw + LM::REDI_OFF),
+            reinterpret_cast<uint32_t *>(raw + LM::IMG_OFF), reinterpret_cast<double *>(raw + LM::LOGTAB_OFF)};
+  } else {
+    __shared__ double lds[LM::PADDED];
+    __shared__ double2 s_tw[LM::TWLEN];
+    __shared__ double red_v[LM::FT / 64];
+    __shared__ int red_i[LM::FT / 64];
+    static_assert(sizeof lds + sizeof s_tw + sizeof red_v + sizeof red_i == LM::TOTAL, "coarse_lds.h describes this");
+    return {lds, s_tw, red_v, red_i, nullptr, nullptr};
+  }
+}
+
+// OVL (persistent kinds only): a due channel that follows another in its
+// batch has its head (ring image, table gathers) run under that channel's
+// tail; see "the overlapped head" below
+template <int M, bool OVL = false>
 __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 13 ? 4 : 1) void coarse_kernel(DevState S, DevTables T, int nch) {
   using K = CoarseK<M>;
   const CoarseBins KB = coarse_bins<M>(S);
-  constexpr int L = K::LOG2N, N = 1 << L, FT = N / 16, PADDED = N + N / 16;
+  constexpr int L = K::LOG2N, N = 1 << L, FT = N / 16;
   constexpr int YLEN = K::YHI - K::YLO + 1;
   constexpr bool PERSIST = L == 14;  // launch_coarse
-  __shared__ double lds[PADDED];
-  __shared__ double2 s_tw[TwLds<L>::LEN];
-  __shared__ double red_v[FT / 64];
-  __shared__ int red_i[FT / 64];
+  static_assert(PERSIST || !OVL, "the overlapped head belongs to the persistent walk");
+  const auto sm = coarse_lds<L, YLEN, OVL>();
+  double *const lds = sm.lds;
+  double2 *const s_tw = sm.s_tw;
+  double *const red_v = sm.red_v;
+  int *const red_i = sm.red_i;
   // the wave's number is kept in a scalar register and the lane's is read
   // anew per channel (lane_now): no vector register holds the thread index
   // across the walk
@@ -349,6 +394,22 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
     // batch's first
     HopPro pro{};
     bool have_pro = false;
+    // The overlapped head (OVL).  While the workgroup is in channel c's tail
+    // and a due successor c' is left in the batch, it already runs c''s head:
+    //   before the third transform   c''s HopPro
+    //   under |X|                    c''s ring words -> the image behind ylds
+    //   under the log10 loop         the image's words, bit-reversed, and
+    //                                the table gathers into x[] (dead since
+    //                                |X|), four elements per three iterations
+    //   after the loop's barrier     s_tw, which the image lay over, again
+    //   after the fold's barrier     the mix, and c''s forward transform
+    // pre says that x[] holds c''s snapshot already.  It follows from mask alone,
+    // which every wave derives for itself from state that does not change
+    // under it, so all 16 waves take the same head and execute the same
+    // barriers in the same order.  The batch's first due channel, and so any
+    // channel after a gap between batches, takes the plain head.
+    bool pre = false;
+    double2 x[16];
 #pragma unroll 1
     while (mask) {
       // a thread index of this channel's own: whatever is computed from it is
@@ -366,83 +427,102 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       // ring entry of the hop sample not written yet (the demod segment ended
       // before the sample was pushed): mixer_center has not moved since.  The
       // word goes to the ring and, by the thread that copies its place, into
-      // the LDS image (not read back from memory)
-      int fixj = -1;
-      uint32_t fixw = 0;
-      if (filled <= nk) {
-        const double mc_ptr = S.ds[DS_MC_PTR * C + c];
-        int tint = (int)mc_ptr;
-        if (tint >= WTSIZE) tint = 0;
-        if (tint < 0) tint = WTSIZE - 1;
-        const int16_t xs = S.pcm[(nk & (S.pcm_cap - 1)) * C + c];
-        fixw = (uint32_t)tint | ((uint32_t)(uint16_t)xs << 16);
-        fixj = (int)(nk & (N - 1));
-        if (t == 0) {
-          S.cring[(size_t)c * N + fixj] = fixw;
-          S.ls[LS_FILLED * C + c] = nk + 1;
+      // the LDS image (not read back from memory).
+      // For a successor cc (overlapped head) this runs under its predecessor's
+      // tail, before that channel's hop control: everything read here
+      // (DS_MC_PTR, the PCM word, LS_FILLED through HopPro) is cc's own, which
+      // no other channel's hop control writes; and LS_FILLED, written early,
+      // is not among what a later batch's due test reads (NSAMP, AVAIL,
+      // HOPS_DONE)
+      auto ring_fixup = [&](int cc, long long fil, long long nkk, int tt, int &fj, uint32_t &fw) {
+        fj = -1;
+        fw = 0;
+        if (fil <= nkk) {
+          const double mc_ptr = S.ds[DS_MC_PTR * C + cc];
+          int tint = (int)mc_ptr;
+          if (tint >= WTSIZE) tint = 0;
+          if (tint < 0) tint = WTSIZE - 1;
+          const int16_t xs = S.pcm[(nkk & (S.pcm_cap - 1)) * C + cc];
+          fw = (uint32_t)tint | ((uint32_t)(uint16_t)xs << 16);
+          fj = (int)(nkk & (N - 1));
+          if (tt == 0) {
+            S.cring[(size_t)cc * N + fj] = fw;
+            S.ls[LS_FILLED * C + cc] = nkk + 1;
+          }
         }
-      }
-      CSTAMP(0);
-
-      if (!have_tw) {  // once per workgroup
-        load_tw_lds<L>(s_tw, T.tw, t, FT);
-        have_tw = true;
-      }
-      // ring words -> LDS (uint32, one pad word per 16: the bit-reversed gather
-      // below reads 16-word strides, which would hit 4 of the 64 banks unpadded).
-      // Every wave is past the previous channel's fold here (its last barrier),
-      // so nobody reads the LDS any more; lane 0's hop control only reads red_*
-      uint32_t *ring_lds = reinterpret_cast<uint32_t *>(lds);
-      const uint32_t *ring = S.cring + (size_t)c * N;
-      if constexpr (PERSIST) {
-        // counted: of a thread index read per channel the compiler does not
-        // know that j = t, t + FT, ... makes 16 trips, and a rolled loop
-        // waits for each load before the next
-#pragma unroll
-        for (int i = 0; i < N / FT; ++i) {
-          const int j = t + i * FT;
-          const uint32_t w = ring[j];
-          ring_lds[j + (j >> 4)] = j == fixj ? fixw : w;
-        }
-      } else {
-        for (int j = t; j < N; j += FT) {
-          const uint32_t w = ring[j];
-          ring_lds[j + (j >> 4)] = j == fixj ? fixw : w;
-        }
-      }
-      __syncthreads();
-      CSTAMP(1);
-      double2 x[16];
+      };
       const long long s0 = nk - (N - 1);  // sample of snapshot element 0 (oqpskdemodulator.cpp:359-365)
-      // every element's table entry is gathered before any is waited for (the
-      // compiler would otherwise sink each gather into its element's branch
-      // and wait for it there: 16 round trips one after another)
-      double2 cs[16];
-      double dval[16];
+      if (!(OVL && pre)) {
+        int fixj;
+        uint32_t fixw;
+        ring_fixup(c, filled, nk, t, fixj, fixw);
+        CSTAMP(0);
+
+        if (!have_tw) {  // once per workgroup
+          load_tw_lds<L>(s_tw, T.tw, t, FT);
+          // (read in the log10 loop, many barriers on)
+          if constexpr (OVL)
+            if (t < 256) sm.logtab[t] = (&aero_g_log_tab[0][0])[t];
+          have_tw = true;
+        }
+        // ring words -> LDS (uint32, one pad word per 16: the bit-reversed gather
+        // below reads 16-word strides, which would hit 4 of the 64 banks unpadded).
+        // Every wave is past the previous channel's fold here (its last barrier),
+        // so nobody reads the LDS any more; lane 0's hop control only reads red_*
+        uint32_t *ring_lds = reinterpret_cast<uint32_t *>(lds);
+        const uint32_t *ring = S.cring + (size_t)c * N;
+        if constexpr (PERSIST) {
+          // counted: of a thread index read per channel the compiler does not
+          // know that j = t, t + FT, ... makes 16 trips, and a rolled loop
+          // waits for each load before the next
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int q = (int)((s0 + bitrev<L>(epos<L, 0>(t, i))) & (N - 1));
-        const uint32_t w = ring_lds[q + (q >> 4)];
-        dval[i] = ((double)(int16_t)(w >> 16)) / 32768.0;
+          for (int i = 0; i < N / FT; ++i) {
+            const int j = t + i * FT;
+            const uint32_t w = ring[j];
+            ring_lds[j + (j >> 4)] = j == fixj ? fixw : w;
+          }
+        } else {
+          for (int j = t; j < N; j += FT) {
+            const uint32_t w = ring[j];
+            ring_lds[j + (j >> 4)] = j == fixj ? fixw : w;
+          }
+        }
+        __syncthreads();
+        CSTAMP(1);
+        // every element's table entry is gathered before any is waited for (the
+        // compiler would otherwise sink each gather into its element's branch
+        // and wait for it there: 16 round trips one after another)
+        double2 cs[16];
+        double dval[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int q = (int)((s0 + bitrev<L>(epos<L, 0>(t, i))) & (N - 1));
+          const uint32_t w = ring_lds[q + (q >> 4)];
+          dval[i] = ((double)(int16_t)(w >> 16)) / 32768.0;
 #ifdef AERO_X_CISLINE
-        cs[i] = T.cis[w & 0x7];  // timing build: every gather on one line
+          cs[i] = T.cis[w & 0x7];  // timing build: every gather on one line
 #else
-        cs[i] = T.cis[w & 0xFFFF];
+          cs[i] = T.cis[w & 0xFFFF];
 #endif
-      }
+        }
 #pragma unroll
-      for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(cs[i].x), "+v"(cs[i].y));
+        for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(cs[i].x), "+v"(cs[i].y));
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        // entries below zero_before were cleared (AFC, CenterFreqChangedSlot);
-        // entries of samples before the channel's first are the ring's own
-        // contents (zero for a new channel: CIS[0] x 0; a channel that changed
-        // rate keeps the ring it had, mskdemodulator.cpp:94-218)
-        const long long s = s0 + bitrev<L>(epos<L, 0>(t, i));
-        x[i] = s < zero_before ? make_double2(0.0, 0.0) : make_double2(cs[i].x * dval[i], cs[i].y * dval[i]);
+        for (int i = 0; i < 16; ++i) {
+          // entries below zero_before were cleared (AFC, CenterFreqChangedSlot);
+          // entries of samples before the channel's first are the ring's own
+          // contents (zero for a new channel: CIS[0] x 0; a channel that changed
+          // rate keeps the ring it had, mskdemodulator.cpp:94-218)
+          const long long s = s0 + bitrev<L>(epos<L, 0>(t, i));
+          x[i] = s < zero_before ? make_double2(0.0, 0.0) : make_double2(cs[i].x * dval[i], cs[i].y * dval[i]);
+        }
+        __syncthreads();  // the ring image is read: the LDS is the transforms' from here on
+        CSTAMP(2);
       }
-      __syncthreads();  // the ring image is read: the LDS is the transforms' from here on
-      CSTAMP(2);
+      // the due successor of this batch, if any: its head runs under this
+      // channel's tail (OVL)
+      const bool nxt = mask != 0;
+      const int cn = nxt ? csched::channel(wgs, wg, k0 + csched::first(mask)) : c;
       if constexpr (PERSIST) t = tnow();
       // forward FFT
       chain::fft<L, true, false>(x, t, lds, T.tw, s_tw, T.twg);
@@ -468,6 +548,13 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       // values), so both multiplies are the identity here and are skipped.
       if constexpr (PERSIST) t = tnow();
       chain::fft<L, false, true>(x, t, lds, T.twi, s_tw, T.twgi);
+      // OVL: the successor's state, needed when its ring image is written
+      // under |X|; loaded here so that the squares cover the round trip, and
+      // scalar from the third transform on
+      // (unconditionally, of this channel again if there is no successor: a
+      // conditional load comes back out of the scalar registers as a phi)
+      HopPro pn{};
+      if constexpr (OVL) pn = load_pro(S, C, cn);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         // square
@@ -477,11 +564,42 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
         const double im = 2.0 * (x[i].x * x[i].y);
         x[i] = make_double2(r, im);
       }
+      if constexpr (OVL) pn = uni(pn);
       CSTAMP(4);
       if constexpr (PERSIST) t = tnow();
       chain::fft<L, false, false>(x, t, lds, T.tw, s_tw, T.twg);
       CSTAMP(5);
       if constexpr (PERSIST) t = tnow();
+      // OVL: the successor's ring words, coalesced, on their way while the
+      // second half of |X| is computed (issued where half of x[] is dead:
+      // held through all of |X| they spilled)
+      uint32_t rw[16];
+      uint32_t pcmw[8];  // the 16 PCM halves of the successor's ring words, two per register
+      int fixjn = -1;
+      uint32_t fixwn = 0;
+      const long long nkn = (long long)K::HOPN * (pn.hops_done + 1) - 1;
+      if (OVL && nxt) ring_fixup(cn, pn.filled, nkn, t, fixjn, fixwn);
+      if constexpr (OVL) {
+        // no store in flight from here to the end of the log10 loop (lane 0's
+        // of the previous channel's hop control are long done, the fix-up's
+        // are rare): with a store possibly in flight the compiler takes the
+        // counter to be out of order and turns every wait below into a wait
+        // for everything, the gathers included
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+      }
+      auto ring_issue = [&]() {
+        if constexpr (OVL) {
+          if (nxt) {
+            const uint32_t *ringn = S.cring + (size_t)cn * N + fresh(t);
+#pragma unroll
+            for (int i = 0; i < N / FT; ++i) rw[i] = ringn[i * FT];
+          } else {
+            // (defined on this path too, or the words stay live around the walk)
+#pragma unroll
+            for (int i = 0; i < N / FT; ++i) rw[i] = 0;
+          }
+        }
+      };
       // fftshift + smoothing y = 0.9 y + 10 log10(max(|X|,1)) over the bins the
       // fold reads: |X| per bin to LDS first (keeps the log10 out of the
       // register-heavy FFT scope), then a dense log10 loop; the y history (HBM)
@@ -515,14 +633,35 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       if (__all(nr)) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
+          if (i == 8) ring_issue();
           const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
           if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT_NR(x[i].x, x[i].y);
         }
       } else {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
+          if (i == 8) ring_issue();
           const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
           if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT(x[i].x, x[i].y);
+        }
+      }
+      if constexpr (OVL) {
+        // the image (coarse_lds.h): behind ylds[0 .. ypad(YLEN - 1)], which the
+        // other waves are writing, across the rest of lds, s_tw and the spare,
+        // short of red_* (the map's static_asserts).  No image write comes
+        // before the barrier that ends the third transform's exchange
+        // (chain::gx), which this thread has passed: by then every wave has
+        // finished its reads of the exchange (the image lies in lds behind
+        // ylds) and made the transform's last read of s_tw (stages <= 9,
+        // before the exchange).  The thread that copies the fix-up's place
+        // patches the word, as in the plain head
+        if (nxt) {
+          using LM = clds::Map<L, YLEN, OVL>;
+#pragma unroll
+          for (int i = 0; i < N / FT; ++i) {
+            const int j = t + i * FT;
+            sm.img[LM::img(j)] = j == fixjn ? fixwn : rw[i];
+          }
         }
       }
       double yp2 = yload(t + 2 * FT);
@@ -530,25 +669,160 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       CSTAMP(6);
       // the loads that would otherwise sit between two channels, issued here
       // where the log10 loop and the fold hide them: the next due channel's
-      // state (same batch; the first of a batch loads its own) and, on wave 0,
-      // what lane 0's hop control reads
-      have_pro = mask != 0;
-      HopPro pn{};
-      if (have_pro) pn = load_pro(S, C, csched::channel(wgs, wg, k0 + csched::first(mask)));
+      // state (same batch; the first of a batch loads its own; the overlapped
+      // head has it already) and, on wave 0, what lane 0's hop control reads
+      have_pro = nxt;
+      if constexpr (!OVL)
+        if (have_pro) pn = load_pro(S, C, cn);
+      // (OVL: after the log10 loop, under the fold; its 17 registers and the
+      // gathered table entries do not fit beside the loop together)
       HopEpi ep{};
-      if (PERSIST && t < 64) ep = load_epi(S, C, c);
-#pragma unroll 1
-      for (int k = t; k < YLEN; k += FT) {
+      if (PERSIST && !OVL && t < 64) ep = load_epi(S, C, c);
+      double2 twv;
+      auto ycalc = [&](double yold, int k) {
+        // OVL: log's table from LDS.  From memory, each lookup is a vector-
+        // memory load the iteration waits for, and with it (loads count down
+        // in issue order) for every table gather issued before it
+        double lg;
+        if constexpr (OVL)
+          lg = CO_LOG10_TAB(fmax(ylds[ypad(k)], 1.0), sm.logtab);
+        else
+          lg = CO_LOG10(fmax(ylds[ypad(k)], 1.0));
+        const double ynew = yold * 0.9 + 0.1 * 10 * lg;
+        // OVL: to memory after the loop, from ylds (ystore below)
+        if constexpr (!OVL) yg[k] = ynew;
+        ylds[ypad(k)] = ynew;
+      };
+      auto ybody = [&](int k) {
         const double yold = yp0;
         yp0 = yp1;
         yp1 = yp2;
         yp2 = yload(k + 3 * FT);
-        const double ynew = yold * 0.9 + 0.1 * 10 * CO_LOG10(fmax(ylds[ypad(k)], 1.0));
-        yg[k] = ynew;
-        ylds[ypad(k)] = ynew;
+        ycalc(yold, k);
+      };
+      // OVL: elements i0 .. i0 + 3 of the successor's snapshot: their words
+      // from the image, bit-reversed as the plain head reads them, the PCM
+      // halves packed and the table gathers issued into x[] (dead since |X|)
+      const long long s0n = nkn - (N - 1);
+      auto gather4 = [&](auto i0c) {
+        if constexpr (OVL) {
+          using LM = clds::Map<L, YLEN, OVL>;
+          constexpr int i0 = decltype(i0c)::value;
+          if (nxt) {
+#pragma unroll
+            for (int i = i0; i < i0 + 4; ++i) {
+              const int q = (int)((s0n + bitrev<L>(epos<L, 0>(t, i))) & (N - 1));
+              const uint32_t w = sm.img[LM::img(q)];
+              pcmw[i >> 1] = (i & 1) ? (pcmw[i >> 1] | (w & 0xFFFF0000u)) : (w >> 16);
+#ifdef AERO_X_CISLINE
+              x[i] = T.cis[w & 0x7];  // timing build: every gather on one line
+#else
+              x[i] = T.cis[w & 0xFFFF];
+#endif
+            }
+          } else {
+            // No successor: the same number of loads, of the table's entry 0,
+            // of which nothing comes.  x[] and pcmw[] have to be defined on
+            // this path too (otherwise the previous values stay live around
+            // the whole walk), and with loads here as there the two paths
+            // join with the same loads in flight: joined with none in flight
+            // on this one, the compiler counted the iterations' waits for
+            // this path, and on the other they then waited for gathers just
+            // issued.  (One set of unconditional gathers with the index
+            // forced to 0 tipped the register allocation into spilling.)
+#pragma unroll
+            for (int i = i0; i < i0 + 4; ++i) {
+              x[i] = T.cis[0];
+              pcmw[i >> 1] = 0;
+            }
+          }
+        }
+      };
+      if constexpr (OVL) {
+        // The gathers under the log10 loop.  A wave's vector-memory loads
+        // count down in issue order, so a y load issued after a gather is not
+        // usable before that gather is back: the gathers go four elements at
+        // a time ahead of three iterations each, and every iteration's
+        // look-ahead y load is used three iterations on, by when the four
+        // gathers before it have long returned.  The iterations are written
+        // out: a rolled loop moves the look-ahead values from register to
+        // register at its top, which waits for the youngest of them and with
+        // it for every gather in flight.
+        // For the same reason the loop stores nothing to memory: with stores
+        // and loads both in flight the counter tells nothing about either, and
+        // every wait becomes a wait for all.  The new y goes to ylds as always
+        // and from there to memory after the loop (ystore).
+        // All image reads come before the barrier below: past it other waves
+        // write s_tw again, under the image.
+        static_assert((YLEN + FT - 1) / FT <= 12, "four groups of three iterations cover the bins");
+        twv = make_double2(0.0, 0.0);
+        // One iteration, yp holding y[k] on entry and y[k + 3 FT] after.  The
+        // old value is used up (0.9 y) before the new one is asked for, so
+        // that the load can land in the same register: a loaded value handed
+        // on to another register is again a copy that waits for the load.
+        // For the same reason the load is unconditional (a clamped index) and
+        // "no history" (past the bins, yreset) is applied where the value is
+        // used.  Only the last iteration, which not every thread has, can be
+        // skipped, and by whole waves only: a branch around an earlier one
+        // joins paths with different loads in flight, after which the
+        // compiler again waits for everything.
+        constexpr int NIT = (YLEN + FT - 1) / FT;
+        auto ystep = [&](double &yp, auto jc) {
+          constexpr int j = decltype(jc)::value;
+          constexpr bool full = (j + 1) * FT <= YLEN;  // every thread has this iteration
+          static_assert(full || j >= NIT - 1, "one partial iteration, the last");
+          if constexpr (j < NIT) {
+            const int k = t + j * FT;
+            if (full || uni(k) < YLEN) {
+              const bool in = full || k < YLEN;
+#ifdef AERO_X_NOYREAD
+              double a = 20.0 * 0.9;
+#else
+              double a = ((in && !yreset) ? yp : 20.0) * 0.9;
+              asm volatile("" : "+v"(a));
+              if constexpr (j + 3 < NIT) yp = yg[min(k + 3 * FT, YLEN - 1)];
+#endif
+              const double lg = CO_LOG10_TAB(fmax(ylds[ypad(in ? k : YLEN - 1)], 1.0), sm.logtab);
+              const double ynew = a + 0.1 * 10 * lg;
+              if (in) ylds[ypad(k)] = ynew;
+            }
+          }
+        };
+        auto ygroup = [&](auto i0c) {
+          constexpr int g = decltype(i0c)::value / 4;
+          // s_tw's entry, for after the barrier: ahead of the last gathers,
+          // so that waiting for it does not wait for them
+          if (g == 3) twv = T.tw[min(t, TwLds<L>::LEN - 1)];
+          gather4(i0c);
+          ystep(yp0, std::integral_constant<int, 3 * g>());
+          ystep(yp1, std::integral_constant<int, 3 * g + 1>());
+          ystep(yp2, std::integral_constant<int, 3 * g + 2>());
+        };
+        ygroup(std::integral_constant<int, 0>());
+        ygroup(std::integral_constant<int, 4>());
+        ygroup(std::integral_constant<int, 8>());
+        ygroup(std::integral_constant<int, 12>());
+      } else {
+#pragma unroll 1
+        for (int k = t; k < YLEN; k += FT) ybody(k);
       }
       __syncthreads();
       CSTAMP(7);
+      if constexpr (OVL) {
+        // every wave has read the image (the barrier above): s_tw, which it
+        // covered, is written again from the table load_tw_lds read it from
+        // (entry j by thread j, as there), so bit for bit what it was; the
+        // fold's closing barrier publishes it before any wave starts the
+        // successor's forward transform.  (From the table and not saved in
+        // registers: a saved entry would have to be read before the third
+        // transform's exchange and live through it, where the kernel's
+        // register peak is, or cost a barrier of its own before the image.)
+        if (nxt && t < TwLds<L>::LEN) s_tw[t] = twv;
+        // ystore: this thread's new y values, from ylds to memory
+#pragma unroll 1
+        for (int k = t; k < YLEN; k += FT) yg[k] = ylds[ypad(k)];
+        if (t < 64) ep = load_epi(S, C, c);
+      }
       // fold search (coarsefreqestimate.cpp:119-140): first strict maximum above 0
       double bv = 0.0;
       int bi = 0x7fffffff;
@@ -581,6 +855,28 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       // next write of red_* is a whole channel of barriers away
       __syncthreads();
       CSTAMP(8);
+      pre = OVL && nxt;
+      if constexpr (OVL) {
+        // the overlapped head's serial rest: the successor's mix, by today's
+        // expression.  x[] holds the table entries gathered under the log10
+        // loop and the fold, pcmw[] the PCM halves.  Past the barrier above
+        // the waves go straight into the successor's forward transform, with
+        // neither of the plain head's barriers: s_tw is whole again since
+        // before that barrier, and what the transform writes in the LDS
+        // (each wave its own region first) nobody reads any more
+        if (nxt) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(x[i].x), "+v"(x[i].y));
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const uint32_t pw = pcmw[i >> 1];
+            const double dv = ((double)(int16_t)((i & 1) ? (pw >> 16) : (pw & 0xFFFFu))) / 32768.0;
+            const long long s = s0n + bitrev<L>(epos<L, 0>(t, i));
+            x[i] = s < pn.zero_before ? make_double2(0.0, 0.0) : make_double2(x[i].x * dv, x[i].y * dv);
+          }
+        }
+        CSTAMP(2);
+      }
       if (t == 0) {
         if constexpr (!PERSIST) ep = load_epi(S, C, c);
         for (int w = 1; w < FT / 64; ++w) {
@@ -676,11 +972,23 @@ void coarse_read_stamps(unsigned long long *out) {
 
 // grid: the persistent kinds' workgroup limit (the device's CU count or
 // AERO_COARSE_GRID, engine.hip)
-void launch_coarse(hipStream_t st, int mode, const DevState &S, const DevTables &T, int nch, int grid) {
+// overlap: the persistent kinds' overlapped head (AERO_COARSE_OVERLAP,
+// engine.hip); without it every channel takes the plain head
+void launch_coarse(hipStream_t st, int mode, const DevState &S, const DevTables &T, int nch, int grid, bool overlap) {
   const dim3 pg(csched::grid(nch, grid < 1 ? 1 : grid));
   switch (mode) {
-    case MODE_OQPSK: hipLaunchKernelGGL(coarse_kernel<MODE_OQPSK>, pg, dim3(1024), 0, st, S, T, nch); break;
-    case MODE_C8400: hipLaunchKernelGGL(coarse_kernel<MODE_C8400>, pg, dim3(1024), 0, st, S, T, nch); break;
+    case MODE_OQPSK:
+      if (overlap)
+        hipLaunchKernelGGL((coarse_kernel<MODE_OQPSK, true>), pg, dim3(1024), 0, st, S, T, nch);
+      else
+        hipLaunchKernelGGL((coarse_kernel<MODE_OQPSK, false>), pg, dim3(1024), 0, st, S, T, nch);
+      break;
+    case MODE_C8400:
+      if (overlap)
+        hipLaunchKernelGGL((coarse_kernel<MODE_C8400, true>), pg, dim3(1024), 0, st, S, T, nch);
+      else
+        hipLaunchKernelGGL((coarse_kernel<MODE_C8400, false>), pg, dim3(1024), 0, st, S, T, nch);
+      break;
     case MODE_MSK600: hipLaunchKernelGGL(coarse_kernel<MODE_MSK600>, dim3(nch), dim3(512), 0, st, S, T, nch); break;
     case MODE_MSK1200: hipLaunchKernelGGL(coarse_kernel<MODE_MSK1200>, dim3(nch), dim3(512), 0, st, S, T, nch); break;
     case MODE_MSK600_24K:

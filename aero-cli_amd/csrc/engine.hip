@@ -57,7 +57,7 @@ void demod_read_stamps(unsigned long long *);
 void coarse_read_stamps(unsigned long long *);
 void viterbi_read_stamps(unsigned long long *);
 void burst_read_stamps(unsigned long long *);
-void launch_coarse(hipStream_t, int, const DevState &, const DevTables &, int, int);
+void launch_coarse(hipStream_t, int, const DevState &, const DevTables &, int, int, bool);
 void launch_frame(hipStream_t, int, const DevState &, int);
 void launch_viterbi(hipStream_t, int, const DevState &, const DevTables &, int, int);
 // the C channel (cchan.hip)
@@ -192,6 +192,9 @@ struct Group {
   // the persistent coarse kernel's workgroup limit (coarse.hip; OQPSK and the
   // C channel): the device's CU count, or AERO_COARSE_GRID
   int coarse_grid = 1;
+  // its overlapped head (the next due channel's snapshot under this one's
+  // tail): on, or AERO_COARSE_OVERLAP=0 for the plain head everywhere
+  bool coarse_overlap = true;
   ModeGeom g{};
   int device = 0, flags = 0, C = 0, nch = 0;
   std::string tag;  // timing-name prefix ("" for OQPSK, "msk600_", "msk1200_", "msk600_48k_", "msk600_16000_", ...)
@@ -1061,7 +1064,7 @@ int run_pass(Group *e, int flush, bool *more) {
     hipEvent_t a, b;
     if (any_hop) {
       ev_begin(e, "coarse", a, b);
-      launch_coarse(e->st, e->mode, e->S, e->T, e->nch, e->coarse_grid);
+      launch_coarse(e->st, e->mode, e->S, e->T, e->nch, e->coarse_grid, e->coarse_overlap);
       ev_end(e, b);
     }
     if (int rc = issue_viterbi(e)) return rc;  // the previous pass's decode, before this demod
@@ -1283,6 +1286,8 @@ int group_create(aero_engine *E, int mode, int gid, int fs, std::unique_ptr<Grou
     else
       HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
     e->coarse_grid = std::max(cus, 1);
+    const char *co = getenv("AERO_COARSE_OVERLAP");
+    e->coarse_overlap = !co || atoi(co) != 0;
   }
   if (msk_generic(mode)) {
     e->g = msk_geom(msk_bitrate(mode), fs);

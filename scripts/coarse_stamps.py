@@ -32,8 +32,15 @@ out = (ctypes.c_ulonglong * 12)()
 vfn = lib.aero_x_viterbi_stamps
 vfn.argtypes = [ctypes.c_void_p]
 vout = (ctypes.c_ulonglong * 4)()
-names = ['batch scan + state', 'ring to LDS', 'table gathers + mix', 'FFT 1', 'boxcar+iFFT+square', 'FFT 3',
-         'hypot', 'log10 + next loads', 'fold search', 'hop control (lane 0)']
+# With the overlapped head (the default; AERO_COARSE_OVERLAP=0 for the plain one) a channel that
+# follows another in its batch has no head of its own: slots 0 and 1 then count the plain heads
+# only (a batch's first due channel), slot 2 the serial rest (the successor's mix), and the
+# successor's ring words and image stores run inside slot 6, its table gathers inside slot 7, the
+# twiddle write and the y stores inside slot 8.  What the other waves
+# wait for lane 0's hop control shows in wave 0's figures only as the kernel time per hop.
+names = ['batch scan + state (plain heads)', 'ring to LDS (plain heads)', 'gathers + mix / serial mix', 'FFT 1',
+         'boxcar+iFFT+square', 'FFT 3', 'hypot + next ring image', 'log10 + next gathers',
+         'fold + twiddles, y stores', 'hop control (lane 0)']
 order = list(range(10))
 for s in range(steps):
     views = [pool[:, int(o) + s * 4096:int(o) + (s + 1) * 4096] for o in offs]
@@ -51,9 +58,9 @@ tot = sum(out[:10])
 n = out[11]
 print('channels %d, hops %d, s_memtime cycles per hop (wave 0) %.0f' % (C, n, tot / max(n, 1)))
 for k in order:
-    print('  %-20s %9.0f  %5.1f %%' % (names[k], out[k] / max(n, 1), 100.0 * out[k] / max(tot, 1)))
+    print('  %-34s %9.0f  %5.1f %%' % (names[k], out[k] / max(n, 1), 100.0 * out[k] / max(tot, 1)))
 if out[10]:  # the persistent kernel: wave 0's whole time in the kernel
-    print('  %-20s %9.0f  (kernel time per hop %.0f)' % ('turnover', (out[10] - tot) / max(n, 1), out[10] / max(n, 1)))
+    print('  %-34s %9.0f  (kernel time per hop %.0f)' % ('turnover', (out[10] - tot) / max(n, 1), out[10] / max(n, 1)))
 eng.close()
 vn = vout[3]
 print('viterbi jobs %d, s_memtime cycles per job %.0f' % (vn, sum(vout[:3]) / max(vn, 1)))
