@@ -3,6 +3,7 @@
   aero-cli_amd/libaero_engine.so   product: HIP kernels for gfx950 + C ABI
   tools/libaero_synth.so           synthetic Aero P-channel transmitter
   oracle/liboracle.so              test-only CPU restatement (checker)
+  tools/liboracle_tick.so          the same plus a DCD-timer hook (burst-timer checker)
 
 Usage: python aero-cli_amd/build.py [--engine] [--synth] [--oracle] [-j N]
 (no flag = everything).  Object files go to aero-cli_amd/build/.
@@ -182,6 +183,25 @@ def build_oracle():
     return os.path.join(ORACLE_DIR, 'liboracle.so')
 
 
+ORACLETICK_SO = os.path.join(ROOT, 'tools', 'liboracle_tick.so')
+
+
+def build_oracletick():
+    """Test-only: the oracle as it stands plus a hook that runs AeroL's 1 s DCD
+    timer slot between two messages (tools/oracle_tick.cpp, tests/oracle_tick.py).
+    oracle/Makefile's flags; the including file makes the oracle's
+    anonymous-namespace members subobjects of a type outside the main file, and
+    -Bsymbolic keeps its calls inside this library when liboracle.so is loaded
+    beside it."""
+    src = os.path.join(ROOT, 'tools', 'oracle_tick.cpp')
+    deps = [src] + [os.path.join(ORACLE_DIR, f) for f in ('aero_oracle.cpp', 'pub_oracle.cpp', 'aero_oracle.h')]
+    if _stale(ORACLETICK_SO, deps):
+        _run(['g++', '-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Wextra',
+              '-Wno-subobject-linkage', '-Wl,-Bsymbolic', '-shared', '-o', ORACLETICK_SO, src,
+              os.path.join(ORACLE_DIR, 'pub_oracle.cpp'), '-lm'])
+    return ORACLETICK_SO
+
+
 HOST = os.path.join(HERE, 'host')
 BIN = os.path.join(HERE, 'bin')
 HOST_COMMON = ['qstr.cpp', 'output.cpp', 'forwarder.cpp', 'zmq_dl.cpp', 'ini.cpp']
@@ -274,6 +294,7 @@ def build_asan(jobs=4):
 
 def build_all(jobs=4):
     build_oracle()
+    build_oracletick()
     build_synth()
     build_mathhost()
     build_fftsim()

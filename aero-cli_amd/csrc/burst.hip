@@ -21,8 +21,12 @@
  *  demod_burst_kernel  part B, one channel per lane, from the front end's
  *                      val_to_demod ring, each trident decision applied at
  *                      its sample.
+ *  burst_tick_kernel   AERO_F_DCD_TICK_BURST only (both burst kinds): the ticks
+ *                      of AeroL's 1 s DCD timer that the messages ended in this
+ *                      pass carry, at the committed soft position (burst_dev.h).
  *  frame_burst_kernel  AeroL burst framing (UW tolerance 4 within the muw window,
- *                      dummy header, R/T block fill, tests at blockptr 320+192k).
+ *                      dummy header, R/T block fill, tests at blockptr 320+192k;
+ *                      with the flag, updateDCD at every recorded tick).
  *  rt_viterbi_kernel   one wave per R/T test: deinterleave 64 x blockptr/64 and
  *                      Decode_soft of the whole block (jconvolutionalcodec.cpp:88-119).
  * CRC checks and R/T packet handling run on the host (engine.hip).
@@ -206,6 +210,7 @@ __global__ __launch_bounds__(64) void front_burst_kernel(BurstState S, BurstTabl
   // the ring keeps what the demodulator has not read yet
   const long long lim = ls[BL_NSAMP * C] + (BV_LEN - (B_D2 - 1));
   if (end > lim) end = lim;
+  if (S.dcd_tick) end = b_front_bound(S, c, end);  // a pass ends with the demodulator's message
   long long chk_n = ls[BL_CHK_N * C];
   const long long chk_done = ls[BL_CHK_DONE * C];
   if (n0 >= end) return;
@@ -885,6 +890,29 @@ void burst_read_stamps(unsigned long long *out) {
 #endif
 }
 
+// ------------------------------------------------------------ DCD ticks
+// AERO_F_DCD_TICK_BURST, after a pass's demodulator launch (either kind; one
+// channel per lane, a handful of loads): message h has ended where the next
+// one starts (the front end let the demodulator go no further, b_front_bound)
+// or, for the last one pushed, where the pushed samples end once the host has
+// counted it whole.  Its ticks go to the ring at the committed soft position.
+__global__ __launch_bounds__(256) void burst_tick_kernel(BurstState S, int nch) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nch) return;
+  const int C = S.C;
+  long long *ls = S.ls + c;
+  const long long n = ls[BL_NSAMP * C], scommit = ls[BL_SCOMMIT * C];
+  const long long chunk_n = ls[BL_CHUNK_N * C], whole = ls[BL_MSG_END * C];
+  const long long *chunks = S.chunks + (size_t)c * CHUNK_RING;
+  const long long h0 = ls[BL_TICK_H * C];
+  long long h = h0;
+  while (h < whole && (h + 1 < chunk_n ? chunks[(h + 1) & (CHUNK_RING - 1)] <= n : n == ls[BL_AVAIL * C])) {
+    b_msg_end(S, c, h, scommit);
+    h++;
+  }
+  if (h != h0) ls[BL_TICK_H * C] = h;
+}
+
 // --------------------------------------------------------- trident check
 // burstoqpskdemodulator.cpp:343-392 for every check the front end recorded
 // this pass (S.tjobs); each workgroup takes checks blockIdx.x, + gridDim.x, ...
@@ -1034,6 +1062,8 @@ __global__ __launch_bounds__(1024) void trident_kernel(BurstState S, BurstTables
 // burst window ends after 10500 bits, dropping the rest of that group.
 // A lane stops before a new packet would overwrite the block of tests it
 // queued this pass, and after RT_TESTS_PER_PASS tests.
+// TICK: AERO_F_DCD_TICK_BURST (without it the kernel is what it was before the flag existed)
+template <bool TICK>
 __global__ __launch_bounds__(256) void frame_burst_kernel(BurstState S, int nch) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nch) return;
@@ -1042,16 +1072,33 @@ __global__ __launch_bounds__(256) void frame_burst_kernel(BurstState S, int nch)
   long long *ls = S.ls + c;
   const long long E = ls[BL_SCOMMIT * C];
   long long q = ls[BL_SCONS * C];
-  if (q >= E) return;
+  // the DCD ticks burst_tick_kernel recorded and this kernel has not applied
+  // (AERO_F_DCD_TICK_BURST): they stay pending over every early exit below
+  BTicks tk{S.tickpos + (size_t)c * B_TICK_RING, 0, 0};
+  if (TICK) {
+    tk.rec = ls[BL_TICK_REC * C];
+    tk.app = ls[BL_TICK_APP * C];
+  }
+  if (q >= E && tk.app == tk.rec) return;
   int realimag = is[BI_RI * C], muw = is[BI_MUW * C], cntr = is[BI_FCNTR * C], gsl = is[BI_GSL * C];
   uint32_t uwi = (uint32_t)is[BI_UWI * C], uwr = (uint32_t)is[BI_UWR * C];
   int inv_i = is[BI_UWI_INV * C], inv_r = is[BI_UWR_INV * C];
   int datacd = is[BI_DATACD * C], blockptr = is[BI_BLOCKPTR * C], burst = is[BI_BURST_ID * C];
   int skip = is[BI_SKIP_GROUP * C];
+  int cd = TICK ? is[BI_DCD_COUNT * C] : 0;
   const int16_t *soft = S.soft + (size_t)c * B_SOFT_RING;
   uint8_t *blk = S.rtblock + (size_t)c * RT_BLOCK;
   int emitted = 0;
-  for (; q < E; ++q) {
+  long long tick_q = TICK ? tk.at(tk.app) : LLONG_MAX;  // loaded once per tick, not per bit
+  for (;; ++q) {
+    // the ticks due before soft entry q: a tick's position is the end of the
+    // last group its message delivered
+    if (TICK)
+      while (tick_q <= q) {
+        b_dcd_tick(cd, datacd, is[BI_DCD_EDGES * C]);
+        tick_q = tk.at(++tk.app);
+      }
+    if (q >= E) break;
     const int e = soft[q & (B_SOFT_RING - 1)];
     const bool last = (e & B_SOFT_LAST) != 0;
     const int v = e & 0x1FF;
@@ -1116,15 +1163,21 @@ __global__ __launch_bounds__(256) void frame_burst_kernel(BurstState S, int nch)
       cntr = -1;
       if (!datacd) is[BI_DCD_EDGES * C]++;
       datacd = 1;
+      cd = 12;
     }
     if (cntr + 1 == 10500) {  // end of the burst window: Decode returns
       cntr = 1000000000;
       if (datacd) is[BI_DCD_EDGES * C]++;
       datacd = 0;
+      cd = 0;
       if (!last) skip = 1;
     }
   }
   ls[BL_SCONS * C] = q;
+  if (TICK) {
+    ls[BL_TICK_APP * C] = tk.app;
+    is[BI_DCD_COUNT * C] = cd;
+  }
   is[BI_RI * C] = realimag;
   is[BI_MUW * C] = muw;
   is[BI_FCNTR * C] = cntr;
@@ -1216,12 +1269,19 @@ void launch_demod_burst(hipStream_t st, const BurstState &S, const BurstTables &
                      trace);
 }
 
+void launch_burst_tick(hipStream_t st, const BurstState &S, int nch) {
+  hipLaunchKernelGGL(burst_tick_kernel, dim3((nch + 255) / 256), dim3(256), 0, st, S, nch);
+}
+
 void launch_trident(hipStream_t st, const BurstState &S, const BurstTables &T, int nch) {
   hipLaunchKernelGGL(trident_kernel, dim3(std::min(nch * TRI_SLOTS, TRI_GRID)), dim3(1024), 0, st, S, T);
 }
 
 void launch_frame_burst(hipStream_t st, const BurstState &S, int nch) {
-  hipLaunchKernelGGL(frame_burst_kernel, dim3((nch + 255) / 256), dim3(256), 0, st, S, nch);
+  if (S.dcd_tick)
+    hipLaunchKernelGGL(frame_burst_kernel<true>, dim3((nch + 255) / 256), dim3(256), 0, st, S, nch);
+  else
+    hipLaunchKernelGGL(frame_burst_kernel<false>, dim3((nch + 255) / 256), dim3(256), 0, st, S, nch);
 }
 
 void launch_rt_viterbi(hipStream_t st, const BurstState &S, int max_jobs) {

@@ -34,6 +34,8 @@ constexpr int B_STARTSTOP = 9600;  // SPS * 1050
 constexpr int B_SOFT_RING = 16384; // int16 entries: 0..255 soft, 0x100 start of packet, |0x200 last of a group
 constexpr int B_SOFT_MARK = 0x100, B_SOFT_LAST = 0x200;
 constexpr int CHUNK_RING = 256;  // message start samples (lastmse, burstoqpskdemodulator.cpp:264)
+constexpr int B_TICK_RING = 4;   // DCD ticks recorded and not yet applied (AERO_F_DCD_TICK_BURST)
+constexpr int B_TICK_FS = 48000; // AeroL's 1 s timer on the sample clock of a burst channel
 constexpr int RT_BLOCK = 6080;   // 64 x 95 R/T block
 constexpr int RT_JOB_OUT = 400;  // int4 header + decoded bits, MSB first
 constexpr int RT_TESTS_PER_PASS = 8;
@@ -84,6 +86,7 @@ enum BIS : int {
   BI_RI, BI_MUW, BI_FCNTR, BI_GSL, BI_UWI, BI_UWR, BI_UWI_INV, BI_UWR_INV, BI_DATACD, BI_BLOCKPTR, BI_BURST_ID,
   BI_SKIP_GROUP,
   BI_DCD_EDGES,  // DataCarrierDetect changes (SignalHunter::handleDcd, decode/hunter.cpp:14-19)
+  BI_DCD_COUNT,  // AeroL datacdcountdown (AERO_F_DCD_TICK_BURST; aerol.cpp:2008-2028, 1043-1058)
   BI_COUNT
 };
 
@@ -124,6 +127,7 @@ enum BMIS : int {
   // AeroL MSK burst framing
   BMI_MUW, BMI_FCNTR, BMI_UW, BMI_UW_INV, BMI_BLOCKPTR, BMI_BURST_ID, BMI_SKIP_GROUP, BMI_TOTAL,
   BMI_DATACD, BMI_DCD_EDGES,  // AeroL datacd (aerol.cpp:2010-2028) and its changes
+  BMI_DCD_COUNT,              // AeroL datacdcountdown (AERO_F_DCD_TICK_BURST)
   BMI_COUNT
 };
 constexpr int BURST_DS_COUNT = BD_COUNT > BM_COUNT ? BD_COUNT : BM_COUNT;
@@ -142,6 +146,11 @@ enum BLS : int {
   BL_NSAMP_A,  // samples through the front end
   BL_CHK_N,    // trident checks recorded by the front end
   BL_CHK_DONE, // trident decisions applied by the demodulator
+  // AERO_F_DCD_TICK_BURST (all zero without it)
+  BL_MSG_END,  // messages pushed whole (the last piece of a long message counts it)
+  BL_TICK_H,   // messages that have ended, their ticks recorded: the message the demodulator is in
+  BL_TICK_REC, // DCD ticks recorded (burst_tick_kernel)
+  BL_TICK_APP, // DCD ticks applied by the framing
   BL_COUNT
 };
 
@@ -179,7 +188,14 @@ struct BurstState {
   int *njobs;
   uint8_t *jobout;              // [C * RT_TESTS_PER_PASS][RT_JOB_OUT]
   double *tri_abs;              // [TRI_GRID][TRI_N] |base| scratch of the trident check
+  // AERO_F_DCD_TICK_BURST (burst_dev.h)
+  int dcd_tick;
+  int *mticks;                  // [C][CHUNK_RING] DCD ticks message k carries (those of the seconds it completes)
+  long long *tickpos;           // [C][B_TICK_RING] committed soft position of each recorded tick
+  int *err;                     // [1] mapped pinned device-error word (BERR_*), sticky; read by the host
 };
+
+constexpr int BERR_TICKS = 2;  // DCD ticks recorded faster than the framing applied them
 
 struct BurstTables {
   const double2 *cis;     // [WTSIZE]

@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 #include "aero_math.h"
 #include "burst_common.h"
 #include "engine_common.h"
@@ -259,6 +261,70 @@ __device__ __forceinline__ double2 dly_int2(double2 *ring, int C, int &p, int si
   p = p + 1 == size ? 0 : p + 1;
   return make_double2(0.0 * newer.x + (1.0 - 0.0) * older.x, 0.0 * newer.y + (1.0 - 0.0) * older.y);
 }
+
+// ---- AeroL's 1 s DCD timer on burst channels (AERO_F_DCD_TICK_BURST).
+// The reference's timer slot runs from the event loop, between two writeData
+// calls: the tick of sample 48000 k - 1 fires at the end of the message that
+// holds that sample, after every soft-bit group the message delivered and
+// before the next message's first.  The host counts the ticks a message
+// carries (S.mticks, beside the message start in S.chunks).  The demodulators'
+// sample loops know nothing of it: with the flag the front end stops a pass
+// at the end of the message the demodulator is in (b_front_bound), so the
+// demodulator's launch ends there too, and burst_tick_kernel, launched after
+// it, records the committed soft position once per tick of a message that
+// has ended; the framing applies a tick when its consume position reaches it.
+
+// BL_TICK_H is the message the demodulator is in (every message before it has
+// ended and its ticks are recorded); the front end goes no further than the
+// start of the next one.
+__device__ __forceinline__ long long b_front_bound(const BurstState &S, int c, long long end) {
+  const int C = S.C;
+  const long long *ls = S.ls + c;
+  const long long next = ls[BL_TICK_H * C] + 1;
+  if (next < ls[BL_CHUNK_N * C]) {
+    const long long start = S.chunks[(size_t)c * CHUNK_RING + (next & (CHUNK_RING - 1))];
+    if (start < end) end = start;
+  }
+  return end;
+}
+
+// the ticks of message h, which ended with `scommit` soft entries handed to
+// the framing (an open group belongs to the next message's first emission)
+__device__ __forceinline__ void b_msg_end(const BurstState &S, int c, long long h, long long scommit) {
+  const int C = S.C;
+  long long *ls = S.ls + c;
+  for (int k = S.mticks[(size_t)c * CHUNK_RING + (h & (CHUNK_RING - 1))]; k > 0; --k) {
+    const long long rec = ls[BL_TICK_REC * C];
+    if (rec - ls[BL_TICK_APP * C] >= B_TICK_RING) {  // the framing lags: nothing overwritten, the run fails
+      if (S.err) __hip_atomic_store(S.err, BERR_TICKS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      break;
+    }
+    S.tickpos[(size_t)c * B_TICK_RING + (rec & (B_TICK_RING - 1))] = scommit;
+    ls[BL_TICK_REC * C] = rec + 1;
+  }
+}
+
+// AeroL::updateDCD (aerol.cpp:1043-1058), the reference's order kept: a
+// negative countdown is clamped only at the next tick
+__device__ __forceinline__ void b_dcd_tick(int &cd, int &datacd, int &edges) {
+  if (cd > 0)
+    cd -= 3;
+  else if (cd < 0)
+    cd = 0;
+  if (datacd && !cd) {
+    datacd = 0;
+    edges++;
+  }
+}
+
+// the framing's view of the recorded ticks: the soft position of tick k
+struct BTicks {
+  const long long *pos;
+  long long rec, app;
+  __device__ __forceinline__ long long at(long long k) const {
+    return k < rec ? pos[k & (B_TICK_RING - 1)] : LLONG_MAX;
+  }
+};
 
 }  // namespace
 }  // namespace aero

@@ -23,7 +23,7 @@ int burst_open(BurstGroup *g, int bitrate, bool disable_reassembly, int *local);
 int burst_close(BurstGroup *g, int c);
 struct LayoutRec;
 size_t burst_layout_plan(int kind, int C, LayoutRec *rec);  // slot_reset.h: the pool's arrays; returns the pool size
-int burst_push(BurstGroup *g, int c, const int16_t *pcm, size_t n, bool dev, bool msg_start);
+int burst_push(BurstGroup *g, int c, const int16_t *pcm, size_t n, bool dev, bool msg_start, bool msg_end);
 int burst_push_batch(BurstGroup *g, const int16_t *src, size_t n, size_t ld, int nch, bool dev);
 int burst_run(BurstGroup *g, int flush);
 int burst_sync(BurstGroup *g);

@@ -43,6 +43,7 @@ void launch_hilbert(hipStream_t st, const BurstState &S, const BurstTables &T, i
 void launch_front_burst(hipStream_t st, const BurstState &S, const BurstTables &T, int nch);
 void launch_demod_burst(hipStream_t st, const BurstState &S, const BurstTables &T, int nch, int trace);
 void launch_trident(hipStream_t st, const BurstState &S, const BurstTables &T, int nch);
+void launch_burst_tick(hipStream_t st, const BurstState &S, int nch);
 void launch_frame_burst(hipStream_t st, const BurstState &S, int nch);
 void launch_rt_viterbi(hipStream_t st, const BurstState &S, int max_jobs);
 void burst_msk_upload_constants(const double *sr_b, const double *sr_a, const double *taps);
@@ -100,13 +101,19 @@ __global__ __launch_bounds__(256) void b_batch_scatter_kernel(int16_t *ring, lon
   }
 }
 
-// the batch's message starts and pushed counts (after the scatter read them)
-__global__ void b_batch_counts_kernel(long long *ls, long long *chunks, int C, int nch, long long n) {
+// the batch's message starts and pushed counts (after the scatter read them);
+// `mticks` (AERO_F_DCD_TICK_BURST, else null): the DCD ticks each message
+// carries, one per multiple of 48000 samples it completes, as burst_push counts them
+__global__ void b_batch_counts_kernel(long long *ls, long long *chunks, int *mticks, int C, int nch, long long n) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= nch) return;
   const long long start = ls[(size_t)BL_AVAIL * C + j];
   const long long k = ls[(size_t)BL_CHUNK_N * C + j];
   chunks[(size_t)j * CHUNK_RING + (k & (CHUNK_RING - 1))] = start;
+  if (mticks) {
+    mticks[(size_t)j * CHUNK_RING + (k & (CHUNK_RING - 1))] = (int)((start + n) / B_TICK_FS - start / B_TICK_FS);
+    ls[(size_t)BL_MSG_END * C + j] = k + 1;
+  }
   ls[(size_t)BL_CHUNK_N * C + j] = k + 1;
   ls[(size_t)BL_AVAIL * C + j] = start + n;
 }
@@ -182,6 +189,10 @@ struct BurstGroup {
   std::vector<double> init_ds;  // [field][channel - init_lo]
   std::vector<int> init_is;
   std::vector<int> since_run;      // messages pushed since the last run (message-start ring)
+  // AERO_F_DCD_TICK_BURST: the DCD ticks of the message being pushed (a long
+  // message arrives in pieces), and the kernels' error word
+  std::vector<int> msg_ticks;
+  int *h_err = nullptr;
   // slots closed channels left (burst_close), the smallest reused first by
   // burst_open; reset_pending: slot -> scalar-init index of those whose device
   // state awaits the reset kernel (burst_flush_reset)
@@ -255,6 +266,8 @@ size_t burst_layout(int kind, BurstState &S, BurstTables &T, int C, char *base, 
   shared(S.ntjobs, 16);
   row(S.msema, (size_t)(msk ? M_MSEMA : B_MSEMA));
   row(S.chunks, (size_t)CHUNK_RING);
+  row(S.mticks, (size_t)CHUNK_RING);
+  row(S.tickpos, (size_t)B_TICK_RING);
   row(S.soft, (size_t)B_SOFT_RING);
   S.hop_cap = B_HOP_CAP;
   row(S.hops, (size_t)B_HOP_CAP * 6);
@@ -336,6 +349,9 @@ int launch_pass(BurstGroup *g, bool trace) {
     timed(g, "burst_trident", [&] { launch_trident(g->st, g->S, g->T, nch); });
     timed(g, "burst_demod", [&] { launch_demod_burst(g->st, g->S, g->T, nch, trace ? 1 : 0); });
   }
+  // AERO_F_DCD_TICK_BURST: the DCD ticks of the messages that ended in this
+  // pass (the front end stopped it at a message end), for the framing below
+  if (g->S.dcd_tick) timed(g, "burst_tick", [&] { launch_burst_tick(g->st, g->S, nch); });
   BCHK(hipMemsetAsync(g->S.njobs, 0, sizeof(int), g->st));
   if (msk)
     timed(g, "burst_frame", [&] { launch_frame_bmsk(g->st, g->S, nch); });
@@ -531,6 +547,10 @@ int burst_group_create(int device, int flags, int max_channels, int kind, BurstG
   BCHK(hipMemset(g->pool, 0, bytes));
   double2 *hk = nullptr;
   burst_layout(kind, g->S, g->T, g->C, reinterpret_cast<char *>(g->pool), &hk);
+  g->S.dcd_tick = (flags & AERO_F_DCD_TICK_BURST) ? 1 : 0;
+  if (hipHostMalloc(&g->h_err, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return AERO_E_NOMEM;
+  *g->h_err = 0;
+  BCHK(hipHostGetDevicePointer((void **)&g->S.err, g->h_err, 0));
   BCHK(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking));
   // tables (host glibc, g++-compiled: tables_host.cpp)
   std::vector<double> cis(2 * WTSIZE), tw8(2 * 8192), twi8(2 * 8192), tw16(2 * 16384), twi16(2 * 16384);
@@ -612,6 +632,7 @@ void burst_group_destroy(BurstGroup *g) {
   if (g->d_reset_slots) (void)hipFree(g->d_reset_slots);
   slot_copier_free(g->copier);
   if (g->pool) (void)hipFree(g->pool);
+  if (g->h_err) (void)hipHostFree(g->h_err);
   if (g->st) (void)hipStreamDestroy(g->st);
   delete g;
 }
@@ -670,6 +691,7 @@ static void burst_host_reset(BurstGroup *g, int c, bool disable_reassembly) {
   g->packets_hold[c].clear();
   g->hb_base[c] = 0;
   g->since_run[c] = 0;
+  g->msg_ticks[c] = 0;
   g->tsu[c] = 0;
   g->tblocks[c] = 0;
 }
@@ -709,6 +731,7 @@ int burst_open(BurstGroup *g, int bitrate, bool disable_reassembly, int *local) 
   g->packets_hold.emplace_back();
   g->hb_base.push_back(0);
   g->since_run.push_back(0);
+  g->msg_ticks.push_back(0);
   g->tsu.push_back(0);
   g->tblocks.push_back(0);
   g->is_free.push_back(0);
@@ -840,11 +863,12 @@ int burst_run(BurstGroup *g, int flush) {
     g->hb_base[c] = (g->avail[c] / HB_SNZ) * HB_SNZ;
     g->since_run[c] = 0;
   }
+  if (*(volatile int *)g->h_err) return AERO_E_DEVICE;  // BERR_TICKS: a DCD tick was dropped (sticky)
   return AERO_OK;
 }
 
 // one message (Decoder::audioReceived -> BurstOqpskDemodulator::dataReceived)
-int burst_push(BurstGroup *g, int c, const int16_t *pcm, size_t n, bool dev, bool msg_start) {
+int burst_push(BurstGroup *g, int c, const int16_t *pcm, size_t n, bool dev, bool msg_start, bool msg_end) {
   if (!n) return AERO_OK;
   BCHK(hipSetDevice(g->device));
   if (int rc = flush_init(g)) return rc;
@@ -880,6 +904,19 @@ int burst_push(BurstGroup *g, int c, const int16_t *pcm, size_t n, bool dev, boo
     g->since_run[c]++;
   }
   g->avail[c] = start + (long long)n;
+  if (g->S.dcd_tick) {
+    // AeroL's 1 s timer on the channel's sample clock: this piece completes
+    // (start + n) / 48000 - start / 48000 seconds; the message carries the
+    // ticks of all its pieces to its end, where burst_tick_kernel records them
+    if (msg_start) g->msg_ticks[c] = 0;
+    g->msg_ticks[c] += (int)(g->avail[c] / B_TICK_FS - start / B_TICK_FS);
+    if (msg_end) {
+      const long long k = g->chunk_n[c] - 1;  // this message
+      BCHK(hipMemcpyAsync(g->S.mticks + (size_t)c * CHUNK_RING + (k & (CHUNK_RING - 1)), &g->msg_ticks[c], 4,
+                          hipMemcpyHostToDevice, g->st));
+      BCHK(hipMemcpyAsync(g->S.ls + (size_t)BL_MSG_END * C + c, &g->chunk_n[c], 8, hipMemcpyHostToDevice, g->st));
+    }
+  }
   BCHK(hipMemcpyAsync(g->S.ls + (size_t)BL_CHUNK_N * C + c, &g->chunk_n[c], 8, hipMemcpyHostToDevice, g->st));
   BCHK(hipMemcpyAsync(g->S.ls + (size_t)BL_AVAIL * C + c, &g->avail[c], 8, hipMemcpyHostToDevice, g->st));
   BCHK(hipStreamSynchronize(g->st));  // the host values copied above and the caller's buffer are free again
@@ -919,8 +956,8 @@ int burst_push_batch(BurstGroup *g, const int16_t *src, size_t n, size_t ld, int
   const dim3 tiles((unsigned)(((long long)n + BTILE - 1) / BTILE), (unsigned)((nch + BTILE - 1) / BTILE));
   hipLaunchKernelGGL(b_batch_scatter_kernel, tiles, dim3(256), 0, g->st, g->S.pcm, B_PCM_CAP, d, (long long)n,
                      (long long)ld, nch, (const long long *)(g->S.ls + (size_t)BL_AVAIL * C));
-  hipLaunchKernelGGL(b_batch_counts_kernel, dim3((nch + 255) / 256), dim3(256), 0, g->st, g->S.ls, g->S.chunks, C,
-                     nch, (long long)n);
+  hipLaunchKernelGGL(b_batch_counts_kernel, dim3((nch + 255) / 256), dim3(256), 0, g->st, g->S.ls, g->S.chunks,
+                     g->S.dcd_tick ? g->S.mticks : nullptr, C, nch, (long long)n);
   BCHK(hipGetLastError());
   for (int c = 0; c < nch; c++) {
     g->chunk_n[c]++;

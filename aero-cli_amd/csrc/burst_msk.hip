@@ -101,6 +101,7 @@ __global__ __launch_bounds__(64) void front_bmsk_kernel(BurstState S, BurstTable
   long long end = ls[BL_AVAIL * C];
   const long long lim = ls[BL_NSAMP * C] + (MV_LEN - (M_D2 - 1));  // what the demodulator has not read
   if (end > lim) end = lim;
+  if (S.dcd_tick) end = b_front_bound(S, c, end);  // a pass ends with the demodulator's message
   long long chk_n = ls[BL_CHK_N * C];
   const long long chk_done = ls[BL_CHK_DONE * C];
   if (n0 >= end) return;
@@ -784,6 +785,8 @@ __global__ __launch_bounds__(1024) void trident_bmsk_kernel(BurstState S, BurstT
 // burst window ends after ifb * 3 bits, dropping the rest of that group.
 // A lane stops before a new packet would overwrite the block of tests it
 // queued this pass, and after RT_TESTS_PER_PASS tests.
+// TICK: AERO_F_DCD_TICK_BURST (without it the kernel is what it was before the flag existed)
+template <bool TICK>
 __global__ __launch_bounds__(256) void frame_bmsk_kernel(BurstState S, int nch) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nch) return;
@@ -792,16 +795,30 @@ __global__ __launch_bounds__(256) void frame_bmsk_kernel(BurstState S, int nch) 
   long long *ls = S.ls + c;
   const long long E = ls[BL_SCOMMIT * C];
   long long q = ls[BL_SCONS * C];
-  if (q >= E) return;
+  // the DCD ticks recorded and not yet applied (AERO_F_DCD_TICK_BURST), as in frame_burst_kernel
+  BTicks tk{S.tickpos + (size_t)c * B_TICK_RING, 0, 0};
+  if (TICK) {
+    tk.rec = ls[BL_TICK_REC * C];
+    tk.app = ls[BL_TICK_APP * C];
+  }
+  if (q >= E && tk.app == tk.rec) return;
   int muw = is[BMI_MUW * C], cntr = is[BMI_FCNTR * C];
   uint32_t uw = (uint32_t)is[BMI_UW * C];
   int inv = is[BMI_UW_INV * C], blockptr = is[BMI_BLOCKPTR * C], burst = is[BMI_BURST_ID * C];
   int skip = is[BMI_SKIP_GROUP * C];
   const int total = is[BMI_TOTAL * C];
+  int cd = TICK ? is[BMI_DCD_COUNT * C] : 0;
   const int16_t *soft = S.soft + (size_t)c * B_SOFT_RING;
   uint8_t *blk = S.rtblock + (size_t)c * RT_BLOCK;
   int emitted = 0;
-  for (; q < E; ++q) {
+  long long tick_q = TICK ? tk.at(tk.app) : LLONG_MAX;
+  for (;; ++q) {
+    if (TICK)
+      while (tick_q <= q) {  // the ticks due before soft entry q
+        b_dcd_tick(cd, is[BMI_DATACD * C], is[BMI_DCD_EDGES * C]);
+        tick_q = tk.at(++tk.app);
+      }
+    if (q >= E) break;
     const int e = soft[q & (B_SOFT_RING - 1)];
     const bool last = (e & B_SOFT_LAST) != 0;
     const int v = e & 0x1FF;
@@ -856,6 +873,7 @@ __global__ __launch_bounds__(256) void frame_bmsk_kernel(BurstState S, int nch) 
         is[BMI_DATACD * C] = 1;
         is[BMI_DCD_EDGES * C]++;
       }
+      cd = 12;
     }
     if (cntr + 1 == total) {  // end of the burst window: Decode returns
       cntr = 1000000000;
@@ -863,10 +881,15 @@ __global__ __launch_bounds__(256) void frame_bmsk_kernel(BurstState S, int nch) 
         is[BMI_DATACD * C] = 0;
         is[BMI_DCD_EDGES * C]++;
       }
+      cd = 0;
       if (!last) skip = 1;
     }
   }
   ls[BL_SCONS * C] = q;
+  if (TICK) {
+    ls[BL_TICK_APP * C] = tk.app;
+    is[BMI_DCD_COUNT * C] = cd;
+  }
   is[BMI_MUW * C] = muw;
   is[BMI_FCNTR * C] = cntr;
   is[BMI_UW * C] = (int)uw;
@@ -897,7 +920,10 @@ void launch_trident_bmsk(hipStream_t st, const BurstState &S, const BurstTables 
 }
 
 void launch_frame_bmsk(hipStream_t st, const BurstState &S, int nch) {
-  hipLaunchKernelGGL(frame_bmsk_kernel, dim3((nch + 255) / 256), dim3(256), 0, st, S, nch);
+  if (S.dcd_tick)
+    hipLaunchKernelGGL(frame_bmsk_kernel<true>, dim3((nch + 255) / 256), dim3(256), 0, st, S, nch);
+  else
+    hipLaunchKernelGGL(frame_bmsk_kernel<false>, dim3((nch + 255) / 256), dim3(256), 0, st, S, nch);
 }
 
 }  // namespace aero

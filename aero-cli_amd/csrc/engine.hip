@@ -2148,7 +2148,7 @@ const char *aero_strerror(int rc) {
     case AERO_E_NOGPU: return "no usable gfx950 device";
     case AERO_E_FULL: return "channel table or ring full";
     case AERO_E_RATE: return "sample rate mismatch";
-    case AERO_E_DEVICE: return "device error: a demod wave hand-off timed out (outputs invalid)";
+    case AERO_E_DEVICE: return "device error: a demod wave hand-off timed out or a DCD tick was dropped (outputs invalid)";
     default: return "unknown error";
   }
 }
@@ -2461,7 +2461,7 @@ int push_burst(aero_engine *e, BurstGroup *bg, int b, const int16_t *pcm, size_t
   size_t off = 0;
   while (off < n) {
     const size_t piece = std::min<size_t>(n - off, 16384);
-    if (int rc = burst_push(bg, b, pcm + off, piece, dev, off == 0)) return rc;
+    if (int rc = burst_push(bg, b, pcm + off, piece, dev, off == 0, off + piece == n)) return rc;
     off += piece;
   }
   return AERO_OK;

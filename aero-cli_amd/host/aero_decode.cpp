@@ -349,10 +349,11 @@ int main(int argc, char **argv) {
   const char *dev = getenv("AERO_DEVICE");
   // the reference runs Qt's event loop (decode/main.cpp:106), so AeroL's 1 s
   // DCD timer fires (decode/aerol.cpp:900-902): the engine runs it on the
-  // sample clock.  AERO_DCD_TICK=0 turns it off (the timer-less behaviour of
-  // a reference without an event loop; test support)
+  // sample clock (--burst: at the end of the message that completes a second,
+  // AERO_F_DCD_TICK_BURST).  AERO_DCD_TICK=0 turns it off (the timer-less
+  // behaviour of a reference without an event loop; test support)
   const char *tick = getenv("AERO_DCD_TICK");
-  const int eflags = (tick && atoi(tick) == 0) ? 0 : AERO_F_DCD_TICK;
+  const int eflags = (tick && atoi(tick) == 0) ? 0 : (AERO_F_DCD_TICK | AERO_F_DCD_TICK_BURST);
   aero_engine_cfg ecfg{dev ? atoi(dev) : 0, (int)topics.size(), eflags};
   if (int rc = aero_engine_create(&ecfg, &eng)) {
     AH_CRIT("Failed to create the MI355X demodulation engine: %s", aero_strerror(rc));

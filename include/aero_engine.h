@@ -29,7 +29,7 @@ extern "C" {
 #define AERO_E_NOGPU (-4)      /* no gfx950 device / kernels not loadable  */
 #define AERO_E_FULL (-5)       /* channel table or PCM ring full           */
 #define AERO_E_RATE (-6)       /* sample rate the channel kind does not serve (MSK: outside [12000, 96000] Hz) */
-#define AERO_E_DEVICE (-7)     /* a kernel gave up (wave hand-off timeout): the run's outputs are invalid */
+#define AERO_E_DEVICE (-7)     /* a kernel gave up (wave hand-off timeout, a DCD tick ring overrun): the run's outputs are invalid */
 
 /* engine flags */
 #define AERO_F_TRACE_PT 0x1    /* keep the rotated pt_qpsk trace (parity tests)      */
@@ -45,7 +45,32 @@ extern "C" {
                                   second of real-time audio (decode/main.cpp:106).
                                   Without it the timer never fires: after a lost
                                   message a channel that has synced once searches
-                                  for the UW only at the expected frame boundary */
+                                  for the UW only at the expected frame boundary.
+                                  Continuous OQPSK only: burst channels ignore it
+                                  (AERO_F_DCD_TICK_BURST is theirs) */
+#define AERO_F_DCD_TICK_BURST 0x80 /* burst channels (10500 OQPSK, 600/1200 MSK): run
+                                  the same timer.  A sync sets datacd and a countdown
+                                  of 12 that only the timer takes down (the burst
+                                  window ends after 10500 soft bits, several bursts
+                                  later, decode/aerol.cpp:2008-2028); the fourth
+                                  tick after a sync clears datacd and reopens the UW
+                                  search for the next burst.  The reference's timer
+                                  slot runs from the event loop, between two
+                                  writeData calls, and a burst channel's output
+                                  depends on message boundaries anyway, so the tick
+                                  of sample 48000 k - 1 (counted from the channel's
+                                  open) fires at the end of the message (one
+                                  aero_push_pcm* call) that holds that sample: after
+                                  every soft-bit group that message delivered to
+                                  AeroL::Decode, before the first of the next
+                                  message.  A message that completes several
+                                  seconds carries as many ticks.  Where in real time
+                                  the shipped binary's timer fires is not pinned;
+                                  this placement is, bit for bit, against the oracle
+                                  with the timer slot called there
+                                  (tests/oracle_tick.py).  Burst MSK does not gate
+                                  its sync on datacd: there only the DataCarrierDetect
+                                  changes differ */
 
 typedef struct aero_engine aero_engine;
 
@@ -171,8 +196,8 @@ int aero_channel_export(aero_engine *e, const int *ch, int n, void *dst, size_t 
  * differs from this engine's for the kind (a hash over the kinds, element
  * sizes, rows and fills of the per-channel arrays; not their offsets or the
  * group's size, which may differ), or whose decode-shaping flags differ from
- * the engine's (AERO_F_TRACE_PT, AERO_F_TRACE_BLOCKS, AERO_F_DCD_TICK; the
- * parity traces AERO_F_TRACE_SOFT and AERO_F_TRACE_HOPS are not checked, but
+ * the engine's (AERO_F_TRACE_PT, AERO_F_TRACE_BLOCKS, AERO_F_DCD_TICK,
+ * AERO_F_DCD_TICK_BURST; the parity traces AERO_F_TRACE_SOFT and AERO_F_TRACE_HOPS are not checked, but
  * continue their numbering only between engines that both keep them).  Every
  * length is checked before it is used.  A batch is all or nothing: on any
  * error no channel of it stays open.
