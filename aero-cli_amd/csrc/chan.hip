@@ -1031,7 +1031,7 @@ int aero_chan_feed(aero_chan *c, aero_engine *e, const int *ch) {
   // an event; the next batch waits for it on this stream (no host wait)
   std::vector<int> chs;
   std::vector<const int16_t *> src;
-  std::vector<size_t> n;
+  std::vector<size_t> n, msg;
   std::vector<uint32_t> fs;
   for (int v = 0; v < c->ids.count(); v++) {  // closed ids are not running
     const Vfo &s = c->subs[v];
@@ -1039,11 +1039,13 @@ int aero_chan_feed(aero_chan *c, aero_engine *e, const int *ch) {
     chs.push_back(ch[v]);
     src.push_back(s.out16);
     n.push_back((size_t)c->last_nblk * s.S);
+    msg.push_back((size_t)s.S);  // vfo::process publishes one message per read (vfo.cpp:184)
     fs.push_back((uint32_t)s.out_rate);
   }
   if (chs.empty()) return AERO_OK;
   CHK(hipEventRecord(c->ev_out, c->st));
-  return aero_engine_feed_dev(e, (int)chs.size(), chs.data(), src.data(), n.data(), fs.data(), c->ev_out, c->st);
+  return aero_engine_feed_dev(e, (int)chs.size(), chs.data(), src.data(), n.data(), msg.data(), fs.data(), c->ev_out,
+                              c->st);
 }
 
 int aero_chan_vfo_open(aero_chan *c, const aero_chan_vfo *cfg, int *v_out) {

@@ -1712,15 +1712,22 @@ int push_common(Group *e, const int16_t *src, size_t n, size_t ld, int nch, int 
 // group's stream waits for the producer's audio (event `ready`), one gather
 // launch copies every item into the PCM rings and sets the channels' pushed
 // counters, and the producer's stream then waits for that launch before it
-// may overwrite the audio.  items: (local channel, device source, samples).
-int feed_group(Group *e, const std::vector<std::pair<int, std::pair<const int16_t *, size_t>>> &items,
-               hipEvent_t ready, hipStream_t producer) {
+// may overwrite the audio.  An item is n samples in messages of msg (the last
+// may be shorter); only the C channel, whose prefilter runs once per message,
+// keeps the message ends.
+struct FeedItem {
+  int c;  // local channel
+  const int16_t *src;
+  size_t n, msg;
+};
+
+int feed_group(Group *e, const std::vector<FeedItem> &items, hipEvent_t ready, hipStream_t producer) {
   HOST_TIMER(e, "host_push");
   if (items.empty()) return AERO_OK;
   if (int rc = flush_pending_init(e)) return rc;
   for (auto &it : items) {  // keep the ring from overrunning unprocessed samples
-    const int c = it.first;
-    const long long n = (long long)it.second.second;
+    const int c = it.c;
+    const long long n = (long long)it.n;
     if (n > PCM_CAP / 2) return AERO_E_FULL;
     if (e->avail[c] + n - e->nsamp[c] > PCM_CAP - 2) {
       if (int rc = run_group(e, 0)) return rc;
@@ -1734,17 +1741,20 @@ int feed_group(Group *e, const std::vector<std::pair<int, std::pair<const int16_
   if (!e->ev_feed_done) HIPCHK(hipEventCreateWithFlags(&e->ev_feed_done, hipEventDisableTiming));
   long long mx = 0;
   for (size_t i = 0; i < items.size(); i++) {
-    const int c = items[i].first;
-    const long long n = (long long)items[i].second.second;
+    const int c = items[i].c;
+    const long long n = (long long)items[i].n;
     GatherJob &j = e->pin_gjobs[k][i];
-    j.src = items[i].second.first;
+    j.src = items[i].src;
     j.n = n;
     j.start = e->avail[c];
     j.avail_after = e->avail[c] + n;
     j.c = c;
     j.later = 0;
+    if (e->mode == MODE_C8400) {  // one prefilter block per message of the item
+      const long long msg = items[i].msg ? (long long)items[i].msg : n;
+      for (long long p = 0; p < n; p += msg) e->msg_end[c].push_back(e->avail[c] + std::min(p + msg, n));
+    }
     e->avail[c] += n;
-    if (e->mode == MODE_C8400 && n) e->msg_end[c].push_back(e->avail[c]);  // one message per item
     mx = std::max(mx, n);
   }
   mark_last_jobs(e->pin_gjobs[k], items.size(), e->C);
@@ -2899,13 +2909,13 @@ int aero_device_math(aero_engine *e, int fn, const double *x, const double *y, d
 
 // aero_chan_feed's entry into the engine (engine_internal.h)
 int aero_engine_feed_dev(aero_engine *e, int nitems, const int *ch, const int16_t *const *src, const size_t *n,
-                         const uint32_t *fs, hipEvent_t ready, hipStream_t producer) {
-  if (!e || nitems < 0 || (nitems && (!ch || !src || !n || !fs))) return AERO_E_INVALID;
+                         const size_t *msg, const uint32_t *fs, hipEvent_t ready, hipStream_t producer) {
+  if (!e || nitems < 0 || (nitems && (!ch || !src || !n || !msg || !fs))) return AERO_E_INVALID;
   for (int i = 0; i < nitems; i++)  // a closed channel: nothing of the call is fed
     if (ch[i] >= 0 && ch[i] < (int)e->chmap.size() && e->chmap[ch[i]].first < 0) return AERO_E_INVALID;
   HIPCHK(hipSetDevice(e->device));
   // per group (gid; a rate change below may add a generic-rate group)
-  std::vector<std::vector<std::pair<int, std::pair<const int16_t *, size_t>>>> per(e->groups.size());
+  std::vector<std::vector<FeedItem>> per(e->groups.size());
   std::vector<uint8_t> queued(e->chmap.size(), 0);  // engine channels with an item in per[]
   auto feed_queued = [&]() -> int {
     for (size_t m = 0; m < per.size(); m++)
@@ -2920,9 +2930,11 @@ int aero_engine_feed_dev(aero_engine *e, int nitems, const int *ch, const int16_
     if (!n[i]) continue;
     BurstGroup *bg;
     const int b = route_burst(e, ch[i], &bg);
-    if (b >= 0) {  // burst channels keep one message per call (synchronous copy)
+    if (b >= 0) {  // burst channels: one writeDataSlot call per message (synchronous copies)
       HIPCHK(hipEventSynchronize(ready));
-      if (int rc = push_burst(e, bg, b, src[i], n[i], true)) return rc;
+      const size_t m = msg[i] ? msg[i] : n[i];
+      for (size_t p = 0; p < n[i]; p += m)
+        if (int rc = push_burst(e, bg, b, src[i] + p, std::min(m, n[i] - p), true)) return rc;
       continue;
     }
     int c, rc;
@@ -2938,7 +2950,7 @@ int aero_engine_feed_dev(aero_engine *e, int nitems, const int *ch, const int16_
     if (rc) return rc;
     if (!g || !src[i]) return AERO_E_INVALID;
     if (per.size() < e->groups.size()) per.resize(e->groups.size());
-    per[g->gid].push_back({c, {src[i], n[i]}});
+    per[g->gid].push_back({c, src[i], n[i], msg[i]});
     queued[ch[i]] = 1;
   }
   return feed_queued();

@@ -96,7 +96,11 @@ int aero_chan_pop_iq(aero_chan *c, int m, int8_t *dst, size_t cap, size_t *n);
 /* vfo::transmitData -> ZMQ -> Decoder::audioReceived (vfo.cpp:289-313,
  * decode/decode.cpp:283-366) without the hop: the last batch's audio of every
  * [vfos] entry v with ch[v] >= 0 goes to engine channel ch[v]
- * (aero_push_pcm_dev).  Call once per aero_chan_run. */
+ * (aero_push_pcm_dev).  Each read of the batch is one message, as
+ * vfo::process publishes one per read (vfo.cpp:184): an 8400-bps C channel
+ * prefilters and a burst channel takes (writeDataSlot) every read on its own,
+ * however many reads the batch held; the continuous kinds do not depend on
+ * the message boundaries.  Call once per aero_chan_run. */
 int aero_chan_feed(aero_chan *c, aero_engine *e, const int *ch);
 
 /*

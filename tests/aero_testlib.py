@@ -466,10 +466,11 @@ def c5_audio(v, seconds, seed):
                      ebn0=30.0), (12000 if br == 600 else 24000)
 
 
-def c5_wideband(cfg, seconds, seed=0xC500, noise=0.02):
+def c5_wideband(cfg, seconds, seed=0xC500, noise=0.02, audio=c5_audio):
     """CF32 wideband at cfg's rate: every VFO's audio as an analytic
-    (upper-sideband) signal at its frequency, built per main VFO at 192 kHz
-    and then raised to the receiver rate, plus a complex noise floor."""
+    (upper-sideband) signal at its frequency, built per main VFO at its
+    out_rate and then raised to the receiver rate, plus a complex noise floor.
+    audio(v, seconds, seed) -> (int16 PCM, its rate) is the VFO's signal."""
     from scipy import signal
     fs = cfg['sample_rate']
     n = int(fs * seconds)
@@ -483,7 +484,7 @@ def c5_wideband(cfg, seconds, seed=0xC500, noise=0.02):
         for k, v in enumerate(cfg['vfos']):
             if abs(v['frequency'] - mv['frequency']) >= mrate // 2:
                 continue
-            pcm, arate = c5_audio(v, seconds, seed + 17 * k + 1)
+            pcm, arate = audio(v, seconds, seed + 17 * k + 1)
             x = signal.hilbert(pcm.astype(np.float64) / 32768.0)
             x = signal.resample_poly(x, mrate // arate, 1)[:nm]
             acc[:len(x)] += 0.25 * x * np.exp(2j * np.pi * (v['frequency'] - mv['frequency']) * tm[:len(x)])
@@ -491,3 +492,95 @@ def c5_wideband(cfg, seconds, seed=0xC500, noise=0.02):
         t = np.arange(len(up)) / fs
         out[:len(up)] += up * np.exp(2j * np.pi * (mv['frequency'] - cfg['center_frequency']) * t)
     return out.astype(np.complex64)
+
+
+# ------------------------------------------------------------------ message boundaries
+# The C channel's prefilter runs once per message and a burst message is one
+# writeDataSlot call: their output depends on where the messages are cut
+# (tests/test_gpu_msg_paths.py, tests/test_msg_boundaries.py).
+
+# sizes around the prefilter's 2048-sample blocks, the 32768 maximum, one sample
+RAGGED = (1, 2047, 2048, 2049, 32768, 100, 4096, 12000, 6143, 1, 30000, 2048, 9000)
+
+
+def cut(pcm, sizes):
+    """pcm as consecutive messages of the sizes in `sizes`, cycled to its end"""
+    out, p, k = [], 0, 0
+    while p < len(pcm):
+        out.append(pcm[p:p + sizes[k % len(sizes)]])
+        p += len(out[-1])
+        k += 1
+    return out
+
+
+def c_outputs(o):
+    """what a C channel delivers, in the shape c_take gives the engine's"""
+    return dict(soft=o.softbits(), pt=o.pt(), hops=o.hops(), frames=o.frames(), c_units=o.c_units(),
+                voice=o.voice(), edges=o.events()[0])
+
+
+def c_reference(msgs):
+    o = Oracle(bitrate=8400, trace_pt=True)
+    for m in msgs:
+        o.push(m)
+    return c_outputs(o)
+
+
+def c_take(eng, ch):
+    return dict(soft=eng.softbits(ch), pt=eng.pt(ch), hops=eng.hops(ch), frames=eng.frames(ch),
+                c_units=eng.c_units(ch), voice=eng.voice(ch), edges=eng.channel_events(ch)[0])
+
+
+def c_produced(ref, frame_bytes=1280, units=3, voice=3):
+    """the oracle alone decoded: a comparison with it is not vacuous"""
+    return len(ref['frames']) >= frame_bytes and len(ref['c_units']) >= units and len(ref['voice']) >= voice
+
+
+def c_equal(got, ref, what='', traces=('soft', 'pt', 'hops')):
+    """exact equality of everything a C channel delivers; `traces`: which of
+    soft bits, pt and hop records (f64 as int64 views) the engine's flags kept"""
+    assert c_produced(ref), '%s: the oracle decoded too little' % what
+    if 'soft' in traces:
+        assert len(ref['soft']) > 10000, '%s: the oracle did not lock' % what
+        assert len(got['soft']) == len(ref['soft']) and np.array_equal(got['soft'], ref['soft']), \
+            '%s: soft bits' % what
+    for k in ('pt', 'hops'):
+        if k in traces:
+            assert len(ref[k]) > 0 and got[k].shape == ref[k].shape and \
+                np.array_equal(got[k].view(np.int64), ref[k].view(np.int64)), '%s: %s' % (what, k)
+    assert np.array_equal(got['frames'], ref['frames']), '%s: frames' % what
+    assert np.array_equal(got['c_units'], ref['c_units']), '%s: Call_progress SUs' % what
+    assert got['voice'] == ref['voice'], '%s: voice frames' % what
+    assert got['edges'] == ref['edges'], '%s: DCD changes' % what
+
+
+# A 288-kHz receiver whose reads give its 48-kHz sub-VFOs 12000 samples each:
+# entry 0 carries an 8400-bps C channel, entry 1 10500-bps burst R/T packets
+BOUNDARY_CFG = dict(sample_rate=288000, center_frequency=CENTER, mains=[dict(frequency=CENTER, out_rate=288000)],
+                    vfos=[dict(frequency=CENTER - 60000, data_rate=8400, gain=100.0),
+                          dict(frequency=CENTER + 30000, data_rate=10500, gain=100.0)])
+BOUNDARY_SECONDS = 10.0
+
+
+def boundary_audio(v, seconds, seed):
+    if v['data_rate'] == 8400:
+        return synth_c(seconds=6.0, seed=0xC1A5, carrier=11000.0, ebn0=12.0), 48000
+    # the burst detector wants the noise floor of the 14-dB default: at 18 dB and above it finds no packet
+    return synth_burst(seconds=seconds, seed=0xAE50), 48000
+
+
+_boundary = {}
+
+
+def boundary_input():
+    """(wideband CF32 of BOUNDARY_CFG, the oracle publisher's audio per
+    [vfos] entry, samples per read of the wideband); computed once"""
+    if not _boundary:
+        cfg = BOUNDARY_CFG
+        x = c5_wideband(cfg, BOUNDARY_SECONDS, seed=0xB0DA, audio=boundary_audio)
+        ref = OraclePublisher(cfg['sample_rate'], cfg['center_frequency'], cfg['mains'], cfg['vfos'])
+        x = x[:len(x) // ref.block_len * ref.block_len]
+        ref.process(x)
+        _boundary.update(x=x, audio=[ref.usb(v) for v in range(len(cfg['vfos']))], block_len=ref.block_len,
+                         spb=[ref.info(v)['samples_per_block'] for v in range(len(cfg['vfos']))])
+    return _boundary['x'], _boundary['audio'], _boundary['block_len'], _boundary['spb']
