@@ -3,7 +3,7 @@
   aero-cli_amd/libaero_engine.so   product: HIP kernels for gfx950 + C ABI
   tools/libaero_synth.so           synthetic Aero P-channel transmitter
   oracle/liboracle.so              test-only CPU restatement (checker)
-  tools/liboracle_tick.so          the same plus a DCD-timer hook (burst-timer checker)
+  tools/liboracle_tick.so          the same plus a DCD-timer hook (checker of the burst and continuous-MSK timers)
 
 Usage: python aero-cli_amd/build.py [--engine] [--synth] [--oracle] [-j N]
 (no flag = everything).  Object files go to aero-cli_amd/build/.
@@ -168,7 +168,7 @@ HOSTCHECK_SRCS = [os.path.join(ROOT, 'tools', 'hostcheck.cpp'), os.path.join(CSR
 
 def build_hostcheck(out=HOSTCHECK_SO, extra=()):
     """Test-only CPU harness over the engine's host C++ (acars_host, tables_host)."""
-    deps = HOSTCHECK_SRCS + [os.path.join(CSRC, h) for h in ('acars_host.h', 'chan_blob.h', 'tables_host.h')]
+    deps = HOSTCHECK_SRCS + [os.path.join(CSRC, h) for h in ('acars_host.h', 'chan_blob.h', 'dcd_host.h', 'tables_host.h')]
     if _stale(out, deps):
         _run(['g++'] + CXX_FLAGS + list(extra) + ['-shared', '-o', out] + HOSTCHECK_SRCS + ['-lm'])
     return out

@@ -250,7 +250,13 @@ __global__ __launch_bounds__(256) void frame_kernel(DevState S, int nch) {
 // 32 UW bits per frame.  A job also carries whether the infofield was
 // cleared (cntr == 0) since the previous block, so the host can assemble a
 // frame's SUs from its blocks exactly as infofield is built (aerol.cpp:1509-1520).
-template <int M>
+// TICK: AERO_F_DCD_TICK_CONT (without it the kernel is what it was before the
+// flag existed).  The framing never reads datacd, so the timer's countdown
+// lives on the host, beside the frames' SU CRCs (engine.hip process_slot); it
+// needs this pass's UW syncs in their order among the channel's jobs, which go
+// into S.syncs.  A flagged demod launch ends at the sample that fires the
+// timer, so a tick always lies behind everything this pass consumes.
+template <int M, bool TICK>
 __global__ __launch_bounds__(256) void frame_msk_kernel(DevState S, int nch) {
   constexpr int N = MskK<M>::LEAVER, B = N * 64;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -261,7 +267,10 @@ __global__ __launch_bounds__(256) void frame_msk_kernel(DevState S, int nch) {
   const long long P = ls[LS_SOFT_P * C + c];
   long long q = ls[LS_SOFT_C * C + c];
   const long long E = P - P % 12;  // delivered in groups of 12 (mskdemodulator.cpp:404-407)
+  if (TICK && q >= E) S.syncs[c] = 0;
   if (q >= E) return;
+  unsigned long long syncs = 0;
+  int nsync = 0, listed = 0;
   int cntr = is[IS_CNTR * C + c];
   uint32_t reg = (uint32_t)is[IS_MSK_PD * C + c];
   int frameinfo = is[IS_FRAMEINFO * C + c], lastframeinfo = is[IS_LASTFRAMEINFO * C + c];
@@ -305,12 +314,17 @@ __global__ __launch_bounds__(256) void frame_msk_kernel(DevState S, int nch) {
                             scr_pos, ((cntr - BitsInHeader) == (NumberOfBits - 1) ? 0x100 : 0) | formatid);
         isu_reset = 0;
         since_clear++;
+        if (TICK) listed++;
         scr_pos += has_ov ? B / 2 : (B + 24) / 2 - 25;
         has_ov = 1;
         blkbuf ^= 1;
       }
     }
     if (gotsync) {
+      if (TICK) {
+        if (nsync < DCD_SYNC_MAX) syncs |= (unsigned long long)(listed & 3) << (4 + 2 * nsync);
+        nsync++;
+      }
       if (cntr + 1 != Total) isu_reset = 1;
       cntr = -1;
       scr_pos = 0;
@@ -335,6 +349,14 @@ __global__ __launch_bounds__(256) void frame_msk_kernel(DevState S, int nch) {
   is[IS_HAS_OVERLAP * C + c] = has_ov;
   is[IS_DATACDCD * C + c] = isu_reset;
   is[IS_BLK_SINCE_CLEAR * C + c] = since_clear;
+  if (TICK) {
+    // cannot happen: syncs are 32 bits apart and a pass is one hop (<= 216 bits),
+    // which is less than one block, so a channel lists at most one job; the
+    // record holds 15 syncs and job counts up to 3
+    if ((nsync > DCD_SYNC_MAX || listed > 3) && S.err)
+      __hip_atomic_store(S.err, DERR_TICKS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    S.syncs[c] = syncs | (unsigned long long)(nsync < DCD_SYNC_MAX ? nsync : DCD_SYNC_MAX);
+  }
 }
 
 // ---------------------------------------------------------------- Viterbi
@@ -571,10 +593,17 @@ void launch_frame(hipStream_t st, int mode, const DevState &S, int nch) {
   // MSK framing depends on the AeroL bit rate only
   if (mode == MODE_OQPSK)
     hipLaunchKernelGGL(frame_kernel, g, b, 0, st, S, nch);
-  else if (msk_bitrate(mode) == 600)
-    hipLaunchKernelGGL(frame_msk_kernel<MODE_MSK600>, g, b, 0, st, S, nch);
-  else
-    hipLaunchKernelGGL(frame_msk_kernel<MODE_MSK1200>, g, b, 0, st, S, nch);
+  else if (msk_bitrate(mode) == 600) {
+    if (S.dcd_cont)
+      hipLaunchKernelGGL((frame_msk_kernel<MODE_MSK600, true>), g, b, 0, st, S, nch);
+    else
+      hipLaunchKernelGGL((frame_msk_kernel<MODE_MSK600, false>), g, b, 0, st, S, nch);
+  } else {
+    if (S.dcd_cont)
+      hipLaunchKernelGGL((frame_msk_kernel<MODE_MSK1200, true>), g, b, 0, st, S, nch);
+    else
+      hipLaunchKernelGGL((frame_msk_kernel<MODE_MSK1200, false>), g, b, 0, st, S, nch);
+  }
 }
 
 // max_jobs: an upper bound of the pass's job count (the count itself is read

@@ -215,7 +215,8 @@ __global__ __launch_bounds__(256, 2) void prefilter_blk_kernel(DevState S, DevTa
 }
 
 // OqpskDemodulator::writeData at fb = 8400 (decode/oqpskdemodulator.cpp:331-557)
-template <bool TRACE>
+// TICK: AERO_F_DCD_TICK_CONT (without it the kernel is what it was before the flag existed)
+template <bool TRACE, bool TICK>
 __global__ __launch_bounds__(64) void demod_c_kernel(DevState S, DevTables T, int nch) {
   __shared__ double cij[241][7];
   __shared__ double sct[440];
@@ -233,7 +234,11 @@ __global__ __launch_bounds__(64) void demod_c_kernel(DevState S, DevTables T, in
   const long long pre_end = S.ls[LS_PRE_END * C + c];
   const int hops_done = S.is[IS_HOPS_DONE * C + c];
   const long long boundary = (long long)HOP * (hops_done + 1) - 1;
-  const long long end = pre_end < boundary ? pre_end : boundary;
+  long long end = pre_end < boundary ? pre_end : boundary;
+  // AERO_F_DCD_TICK_CONT: the launch ends with the sample that fires the DCD
+  // timer, whether or not the demod delivers soft bits there (mse above the
+  // threshold: a call's end)
+  if (TICK) end = dcd_cont_end(end, S.ls[LS_TICK_BASE * C + c], S.g.fs, boundary, pre_end);
   const int capm = (int)S.pcm_cap - 1;
   const int ia = (int)(avail - n0);
   const int ie = (int)(end - n0);
@@ -494,6 +499,7 @@ __global__ __launch_bounds__(64) void demod_c_kernel(DevState S, DevTables T, in
     m2_fsum = 0;
   }
   ls[LS_NSAMP * C] = n0 + i;
+  if (TICK && n0 + i == ls[LS_TICK_BASE * C] + S.g.fs) ls[LS_TICK_BASE * C] = n0 + i;  // the timer fired
   ls[LS_FILLED * C] = n0 + ifl;
   ls[LS_SOFT_P * C] = softp;
   if (TRACE) ls[LS_PT_N * C] = ptn;
@@ -790,10 +796,14 @@ void launch_prefilter_c(hipStream_t st, const DevState &S, const DevTables &T, c
 }
 void launch_demod_c(hipStream_t st, const DevState &S, const DevTables &T, int nch, bool trace) {
   const dim3 g((nch + 63) / 64), b(64);
-  if (trace)
-    hipLaunchKernelGGL(demod_c_kernel<true>, g, b, 0, st, S, T, nch);
+  if (trace && S.dcd_cont)
+    hipLaunchKernelGGL((demod_c_kernel<true, true>), g, b, 0, st, S, T, nch);
+  else if (trace)
+    hipLaunchKernelGGL((demod_c_kernel<true, false>), g, b, 0, st, S, T, nch);
+  else if (S.dcd_cont)
+    hipLaunchKernelGGL((demod_c_kernel<false, true>), g, b, 0, st, S, T, nch);
   else
-    hipLaunchKernelGGL(demod_c_kernel<false>, g, b, 0, st, S, T, nch);
+    hipLaunchKernelGGL((demod_c_kernel<false, false>), g, b, 0, st, S, T, nch);
 }
 void launch_frame_c(hipStream_t st, const DevState &S, int nch) {
   hipLaunchKernelGGL(frame_c_kernel, dim3((nch + 255) / 256), dim3(256), 0, st, S, nch);

@@ -66,7 +66,10 @@ __device__ __forceinline__ double diff_soft(double &last, double soft) {  // Dif
 
 }  // namespace
 
-template <int M>
+// TICK (all three kernels): AERO_F_DCD_TICK_CONT, a launch ends with the sample
+// that fires AeroL's DCD timer (engine_common.h dcd_cont_end); without it the
+// kernel is what it was before the flag existed
+template <int M, bool TICK>
 __global__ __launch_bounds__(MskK<M>::WG) void demod_msk_kernel(DevState S, DevTables T, int nch, int flush) {
   using K = MskK<M>;
   constexpr int WG = K::WG;
@@ -117,6 +120,7 @@ __global__ __launch_bounds__(MskK<M>::WG) void demod_msk_kernel(DevState S, DevT
   const long long boundary = (long long)HOPN * (hops_done + 1) - 1;
   long long end = avail < boundary ? avail : boundary;
   if (!flush && avail <= boundary) end = n0;
+  if (TICK) end = dcd_cont_end(end, S.ls[LS_TICK_BASE * C + c], S.g.fs, boundary, avail);
   const int capm = (int)S.pcm_cap - 1;
   const int ia = (int)(avail - n0);
   const int ie = (int)(end - n0);
@@ -418,6 +422,7 @@ __global__ __launch_bounds__(MskK<M>::WG) void demod_msk_kernel(DevState S, DevT
   double *ds = S.ds + cl;
   long long *ls = S.ls + cl;
   ls[LS_NSAMP * C] = n0 + i;
+  if (TICK && n0 + i == ls[LS_TICK_BASE * C] + S.g.fs) ls[LS_TICK_BASE * C] = n0 + i;  // the timer fired
   ls[LS_FILLED * C] = n0 + ifl;
   ls[LS_SOFT_P * C] = softp;
   ls[LS_EVENTS * C] = ev;
@@ -448,6 +453,7 @@ __global__ __launch_bounds__(MskK<M>::WG) void demod_msk_kernel(DevState S, DevT
 // every ring is read at the top of its sample, the libm tables are the
 // global copies.  One 64-lane workgroup per 64 channels.
 constexpr int MSKG_WG = 64;
+template <bool TICK>
 __global__ __launch_bounds__(MSKG_WG) void demod_mskg_kernel(DevState S, DevTables T, int nch, int flush) {
   const MskGen &G = S.mg;
   const int SPS = G.sps, NT = 2 * SPS, AGC = S.g.agc_len, DSM = S.g.dsm_len, D8 = S.g.d8_len, DTL = S.g.dt_len,
@@ -468,6 +474,7 @@ __global__ __launch_bounds__(MSKG_WG) void demod_mskg_kernel(DevState S, DevTabl
   const long long boundary = (long long)HOPN * (hops_done + 1) - 1;
   long long end = avail < boundary ? avail : boundary;
   if (!flush && avail <= boundary) end = n0;
+  if (TICK) end = dcd_cont_end(end, S.ls[LS_TICK_BASE * C + c], S.g.fs, boundary, avail);
   const int capm = (int)S.pcm_cap - 1;
   const int ia = (int)(avail - n0);
   const int ie = (int)(end - n0);
@@ -670,6 +677,7 @@ __global__ __launch_bounds__(MSKG_WG) void demod_mskg_kernel(DevState S, DevTabl
   double *ds = S.ds + c;
   long long *ls = S.ls + c;
   ls[LS_NSAMP * C] = n0 + ie;
+  if (TICK && n0 + ie == ls[LS_TICK_BASE * C] + S.g.fs) ls[LS_TICK_BASE * C] = n0 + ie;  // the timer fired
   ls[LS_FILLED * C] = n0 + ifl;
   ls[LS_SOFT_P * C] = softp;
   ls[LS_EVENTS * C] = ev;
@@ -707,7 +715,7 @@ __global__ __launch_bounds__(MSKG_WG) void demod_mskg_kernel(DevState S, DevTabl
 // a group can switch between the kernels from one launch to the next.
 constexpr int MSKW_G = 16, MSKW_WG = 64;
 static_assert(MAX_TAPS <= 20 * MSKW_G, "launch_demod_msk's largest instance holds every tap");
-template <int B>
+template <int B, bool TICK>
 __global__ __launch_bounds__(MSKW_WG) void demod_mskw_kernel(DevState S, DevTables T, int nch, int flush) {
   const MskGen &G = S.mg;
   const int SPS = G.sps, NT = 2 * SPS, AGC = S.g.agc_len, DSM = S.g.dsm_len, D8 = S.g.d8_len, DTL = S.g.dt_len,
@@ -734,6 +742,7 @@ __global__ __launch_bounds__(MSKW_WG) void demod_mskw_kernel(DevState S, DevTabl
   const long long boundary = (long long)HOPN * (hops_done + 1) - 1;
   long long end = avail < boundary ? avail : boundary;
   if (!flush && avail <= boundary) end = n0;
+  if (TICK) end = dcd_cont_end(end, S.ls[LS_TICK_BASE * C + c], S.g.fs, boundary, avail);
   const int capm = (int)S.pcm_cap - 1;
   const int ia = (int)(avail - n0);
   const int ie = (int)(end - n0);
@@ -983,6 +992,7 @@ __global__ __launch_bounds__(MSKW_WG) void demod_mskw_kernel(DevState S, DevTabl
   double *ds = S.ds + c;
   long long *ls = S.ls + c;
   ls[LS_NSAMP * C] = n0 + ie;
+  if (TICK && n0 + ie == ls[LS_TICK_BASE * C] + S.g.fs) ls[LS_TICK_BASE * C] = n0 + ie;  // the timer fired
   ls[LS_FILLED * C] = n0 + ifl;
   ls[LS_SOFT_P * C] = softp;
   ls[LS_EVENTS * C] = ev;
@@ -1008,7 +1018,10 @@ __global__ __launch_bounds__(MSKW_WG) void demod_mskw_kernel(DevState S, DevTabl
 template <int M>
 static void launch_msk_mode(hipStream_t st, const DevState &S, const DevTables &T, int nch, int flush) {
   constexpr int WG = MskK<M>::WG;
-  hipLaunchKernelGGL(demod_msk_kernel<M>, dim3((nch + WG - 1) / WG), dim3(WG), 0, st, S, T, nch, flush);
+  if (S.dcd_cont)
+    hipLaunchKernelGGL((demod_msk_kernel<M, true>), dim3((nch + WG - 1) / WG), dim3(WG), 0, st, S, T, nch, flush);
+  else
+    hipLaunchKernelGGL((demod_msk_kernel<M, false>), dim3((nch + WG - 1) / WG), dim3(WG), 0, st, S, T, nch, flush);
 }
 
 // the few-channel kernel for nch <= wide_max (engine.hip: up to
@@ -1016,7 +1029,10 @@ static void launch_msk_mode(hipStream_t st, const DevState &S, const DevTables &
 template <int B>
 static void launch_mskw(hipStream_t st, const DevState &S, const DevTables &T, int nch, int flush) {
   constexpr int CPB = MSKW_WG / MSKW_G;
-  hipLaunchKernelGGL(demod_mskw_kernel<B>, dim3((nch + CPB - 1) / CPB), dim3(MSKW_WG), 0, st, S, T, nch, flush);
+  if (S.dcd_cont)
+    hipLaunchKernelGGL((demod_mskw_kernel<B, true>), dim3((nch + CPB - 1) / CPB), dim3(MSKW_WG), 0, st, S, T, nch, flush);
+  else
+    hipLaunchKernelGGL((demod_mskw_kernel<B, false>), dim3((nch + CPB - 1) / CPB), dim3(MSKW_WG), 0, st, S, T, nch, flush);
 }
 
 void launch_demod_msk(hipStream_t st, int mode, const DevState &S, const DevTables &T, int nch, int flush,
@@ -1035,8 +1051,13 @@ void launch_demod_msk(hipStream_t st, int mode, const DevState &S, const DevTabl
     case MODE_MSK600_48K: return launch_msk_mode<MODE_MSK600_48K>(st, S, T, nch, flush);
     case MODE_MSK1200_12K: return launch_msk_mode<MODE_MSK1200_12K>(st, S, T, nch, flush);
     case MODE_MSK1200_48K: return launch_msk_mode<MODE_MSK1200_48K>(st, S, T, nch, flush);
-    default:  // MODE_MSKG600, MODE_MSKG1200
-      hipLaunchKernelGGL(demod_mskg_kernel, dim3((nch + MSKG_WG - 1) / MSKG_WG), dim3(MSKG_WG), 0, st, S, T, nch, flush);
+    default: {  // MODE_MSKG600, MODE_MSKG1200
+      const dim3 g((nch + MSKG_WG - 1) / MSKG_WG), b(MSKG_WG);
+      if (S.dcd_cont)
+        hipLaunchKernelGGL(demod_mskg_kernel<true>, g, b, 0, st, S, T, nch, flush);
+      else
+        hipLaunchKernelGGL(demod_mskg_kernel<false>, g, b, 0, st, S, T, nch, flush);
+    }
   }
 }
 

@@ -39,6 +39,7 @@
 #include "burst_engine.h"
 #include "aero_math.h"
 #include "chan_blob.h"
+#include "dcd_host.h"
 #include "engine_common.h"
 #include "fft_layout.h"
 #include "host_pool.h"
@@ -241,7 +242,17 @@ struct Group {
   std::vector<std::deque<long long>> msg_end;
   std::vector<long long> pre_end;
   std::vector<std::vector<uint8_t>> cunit_hold, voice_hold;
-  std::vector<int> c_cd, c_dcd, c_edges;
+  // AeroL's DCD countdown where the host keeps it (dcd_host.h): the C channel,
+  // and with AERO_F_DCD_TICK_CONT continuous MSK
+  std::vector<DcdHost> dcd;
+  // AERO_F_DCD_TICK_CONT on this group (continuous MSK, C): host mirror of
+  // LS_TICK_BASE; the channels whose demod launch of the pass being queued ends
+  // at a tick (frame_round hands them to the pass's job slot); each channel's
+  // walk through a slot's sync words (process_slot)
+  bool dcd_cont = false;
+  std::vector<long long> tick_base;
+  std::vector<int> pass_ticks;
+  std::vector<DcdPass> dcd_pass;
   void *pin_cjobs[4] = {}, *d_cjobs[4] = {};
   hipEvent_t cjob_ev[4] = {};
   int next_cjob = 0;
@@ -274,6 +285,10 @@ struct Group {
     int *h_n = nullptr;
     uint8_t *h_out_dev = nullptr;  // the same buffers as the device addresses them
     int *h_n_dev = nullptr;
+    // AERO_F_DCD_TICK_CONT: the MSK framing kernel's sync words ([C], mapped
+    // pinned as h_out) and the channels whose pass ended at a tick
+    unsigned long long *h_sync = nullptr, *h_sync_dev = nullptr;
+    std::vector<int> ticks;
     hipEvent_t ev = nullptr;
     bool pending = false;
   };
@@ -334,6 +349,7 @@ struct Group {
   std::atomic<uint64_t> st_jobs{0}, st_frames{0}, st_su_ok{0};
   int init_lo = 0;  // channels [init_lo, nch) await device state init
   std::vector<uint8_t> h_jobs_task, h_dbg_task;  // buffers owned by the running host task
+  std::vector<uint8_t> h_tick_task;              // AERO_F_DCD_TICK_CONT: per channel, its pass ended at a tick
 };
 
 // chmap kinds of burst-mode channels (burst_engine.hip): MODE_BURST + BurstKind
@@ -388,6 +404,7 @@ size_t layout(DevState &S, DevTables &T, int mode, const ModeGeom &g, int C, int
   S.C = C;
   S.mode = mode;
   S.dcd_tick = (mode == MODE_OQPSK && (flags & AERO_F_DCD_TICK)) ? 1 : 0;
+  S.dcd_cont = (mode != MODE_OQPSK && (flags & AERO_F_DCD_TICK_CONT)) ? 1 : 0;
   S.g = g;
   col(S.ds, DS_COUNT, RF_DS);
   col(S.is, IS_COUNT, RF_IS);
@@ -662,13 +679,29 @@ int process_slot(Group *e, int si) {
                          hipMemcpyDeviceToHost));
     }
   }
-  if (njobs <= 0) return AERO_OK;
-  e->st_jobs += (uint64_t)njobs;
   const bool msk = e->mode != MODE_OQPSK && e->mode != MODE_C8400;
   const bool cch = e->mode == MODE_C8400;
+  // AERO_F_DCD_TICK_CONT: each channel's syncs and tick of this pass (dcd_host.h);
+  // a pass without a job still delivers them
+  bool dcd_events = false;
+  if (e->dcd_cont) {
+    for (int c = 0; c < nch; c++) {
+      e->dcd_pass[c] = DcdPass();
+      if (sl.h_sync) e->dcd_pass[c].syncs = sl.h_sync[c];
+      dcd_events |= e->dcd_pass[c].syncs != 0;
+    }
+    e->h_tick_task.assign((size_t)nch, 0);
+    for (int c : sl.ticks)
+      if (c >= 0 && c < nch) e->h_tick_task[c] = 1;
+    dcd_events |= !sl.ticks.empty();
+    sl.ticks.clear();
+  }
+  if (njobs <= 0 && !dcd_events) return AERO_OK;
+  e->st_jobs += (uint64_t)std::max(njobs, 0);
+  const bool dcd_cont = e->dcd_cont;
   // channels partitioned over workers (c % T): a channel's frames stay in
   // queue order and no two workers share state
-  auto work = [e, njobs, nch, blocks, msk, cch, JO](int t, int T) {
+  auto work = [e, njobs, nch, blocks, msk, cch, JO, dcd_cont](int t, int T) {
     const uint8_t *jobs = e->h_jobs_task.data();
     uint64_t frames = 0, su_ok = 0;  // this worker's counts, added once (no shared atomics per job)
     for (int j = 0; j < njobs; j++) {
@@ -686,16 +719,7 @@ int process_slot(Group *e, int si) {
         uint32_t aes = 0;
         for (int k = 0; k < 3; k++) {
           const bool ok = (mask >> k) & 1;
-          int &cd = e->c_cd[c];
-          if (ok) {
-            if (cd < 12) cd += 2;
-          } else {
-            if (cd > 0) cd -= 5;
-          }
-          if (!e->c_dcd[c] && cd > 2) {
-            e->c_dcd[c] = 1;
-            e->c_edges[c]++;
-          }
+          e->dcd[c].su(ok, 5);
           const uint8_t *su = o + 12 * k;
           if (ok && su[0] == 0x30) {
             e->cunit_hold[c].insert(e->cunit_hold[c].end(), su, su + 12);
@@ -727,6 +751,7 @@ int process_slot(Group *e, int si) {
         h.insert(h.end(), d + 4, d + 4 + nb);
       }
       if (reset) e->host[c]->isu_reset();
+      if (dcd_cont) e->dcd_pass[c].job(e->dcd[c]);  // the syncs before this job
       int flen = -1;
       uint32_t mask = (uint32_t)meta[1];
       const uint8_t *info = o;
@@ -741,6 +766,8 @@ int process_slot(Group *e, int si) {
           mask = 0;
           for (int k = 0; k < flen / 12; k++)
             if (su_crc_ok(inf.data() + 12 * k)) mask |= 1u << k;
+          if (dcd_cont)  // the frame's SUs on the DCD countdown (aerol.cpp:1545-1556)
+            for (int k = 0; k < flen / 12; k++) e->dcd[c].su((mask >> k) & 1, 3);
           info = inf.data();
         }
       } else {
@@ -760,6 +787,8 @@ int process_slot(Group *e, int si) {
         }
       }
     }
+    if (dcd_cont)  // the syncs after the last job, then the tick a pass ends with
+      for (int c = t; c < nch; c += T) e->dcd_pass[c].finish(e->dcd[c], e->h_tick_task[c] != 0);
     e->st_frames += frames;
     e->st_su_ok += su_ok;
   };
@@ -1051,10 +1080,16 @@ int run_pass(Group *e, int flush, bool *more) {
       long long end = std::min(e->avail[c], boundary);
       if (!flush && e->avail[c] <= boundary) end = e->nsamp[c];
       if (cch) end = std::min(e->pre_end[c], boundary);  // whole messages, prefiltered
+      // AERO_F_DCD_TICK_CONT: a launch ends with the sample that fires the DCD timer
+      if (e->dcd_cont) end = dcd_cont_end(end, e->tick_base[c], e->g.fs, boundary, cch ? e->pre_end[c] : e->avail[c]);
       if (end > e->nsamp[c]) {
         e->processed += (uint64_t)(end - e->nsamp[c]);
         e->nsamp[c] = end;
         progress = true;
+        if (e->dcd_cont && end == e->tick_base[c] + e->g.fs) {
+          e->tick_base[c] = end;
+          e->pass_ticks.push_back(c);
+        }
       }
     }
     if (!any_hop && !progress && !ncj) {
@@ -1111,6 +1146,9 @@ int frame_round(Group *e, int flush, bool trace) {
     S2.njobs = sl.d_n;
     S2.jobout = nullptr;  // framing lists jobs only; the Viterbi writes the records
     S2.jobs = sl.d_jobs;
+    S2.syncs = sl.h_sync_dev;
+    sl.ticks.swap(e->pass_ticks);  // (the slot's previous pass is handed over: its list is spent)
+    e->pass_ticks.clear();
     HIPCHK(hipMemsetAsync(sl.d_n, 0, sizeof(int), e->st));
     {
       // a channel refills its other interleaver buffer >= 5 passes after a
@@ -1317,6 +1355,7 @@ int group_create(aero_engine *E, int mode, int gid, int fs, std::unique_ptr<Grou
   HIPCHK(hipMemset(e->pool, 0, bytes));
   layout(e->S, e->T, mode, e->g, e->C, e->flags, reinterpret_cast<char *>(e->pool));
   e->S.mg = mg;
+  e->dcd_cont = e->S.dcd_cont != 0;
   HIPCHK(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
   if (hipHostMalloc(&e->h_err, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return AERO_E_NOMEM;
   *e->h_err = 0;
@@ -1332,6 +1371,13 @@ int group_create(aero_engine *E, int mode, int gid, int fs, std::unique_ptr<Grou
     if (hipHostMalloc(&sl.h_n, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return AERO_E_NOMEM;
     HIPCHK(hipHostGetDevicePointer((void **)&sl.h_out_dev, sl.h_out, 0));
     HIPCHK(hipHostGetDevicePointer((void **)&sl.h_n_dev, sl.h_n, 0));
+    if (e->S.dcd_cont && mode != MODE_C8400) {
+      if (hipHostMalloc(&sl.h_sync, sizeof(unsigned long long) * e->C, hipHostMallocMapped | hipHostMallocCoherent) !=
+          hipSuccess)
+        return AERO_E_NOMEM;
+      memset(sl.h_sync, 0, sizeof(unsigned long long) * e->C);
+      HIPCHK(hipHostGetDevicePointer((void **)&sl.h_sync_dev, sl.h_sync, 0));
+    }
     if (hipMalloc(&sl.d_jobs, (size_t)16 * e->C) != hipSuccess) return AERO_E_NOMEM;
     HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&sl.ev_vit, hipEventDisableTiming));
@@ -1471,6 +1517,7 @@ void group_destroy(Group *e) {
     if (sl.ev_framed) (void)hipEventDestroy(sl.ev_framed);
     if (sl.h_out) (void)hipHostFree(sl.h_out);
     if (sl.h_n) (void)hipHostFree(sl.h_n);
+    if (sl.h_sync) (void)hipHostFree(sl.h_sync);
     if (sl.ev) (void)hipEventDestroy(sl.ev);
   }
   if (e->h_err) (void)hipHostFree(e->h_err);
@@ -1847,9 +1894,9 @@ int group_add_channel(aero_engine *e, int gid, const aero_channel_cfg &cfg, int 
   g->pre_end.push_back(0);
   g->cunit_hold.emplace_back();
   g->voice_hold.emplace_back();
-  g->c_cd.push_back(0);
-  g->c_dcd.push_back(0);
-  g->c_edges.push_back(0);
+  g->dcd.emplace_back();
+  g->tick_base.push_back(0);
+  g->dcd_pass.emplace_back();
   if (g->trace_some) g->trace_mask.resize(g->C, 0);
   *local = c;
   return AERO_OK;
@@ -1885,7 +1932,8 @@ void release_slot(aero_engine *e, int gid, int c) {
   g->pre_end[c] = 0;
   g->cunit_hold[c].clear();
   g->voice_hold[c].clear();
-  g->c_cd[c] = g->c_dcd[c] = g->c_edges[c] = 0;
+  g->dcd[c] = DcdHost();  // a reopened slot starts a fresh timer
+  g->tick_base[c] = 0;
   if (g->trace_some && g->trace_mask[c]) {
     g->trace_mask[c] = 0;
     g->trace_list.erase(std::remove(g->trace_list.begin(), g->trace_list.end(), c), g->trace_list.end());
@@ -1963,6 +2011,17 @@ int msk_migrate(aero_engine *e, int ch, uint32_t fs) {
   ls[LS_ZERO_BEFORE] = -(1LL << 62);  // the cleared entries are written as zeros below; the rest is read
   ls[LS_PT_N] = 0;
   ls[LS_EVENTS] = 0;
+  if (g->dcd_cont) {
+    // AeroL is untouched by setSettings: its DCD countdown, datacd and edge
+    // count carry over (the old group drained above, so every tick and CRC of
+    // the old rate is applied), and the elapsed part of the timer's second is
+    // rescaled to the new rate; the sample count restarts at 0, so the base is <= 0
+    const long long fs_old = g->g.fs, fs_new = h->g.fs;
+    const long long left = ls[LS_TICK_BASE] + fs_old - n_old, elapsed = fs_old - left;
+    ls[LS_TICK_BASE] = -((elapsed * fs_new) / fs_old);
+    h->tick_base[c2] = ls[LS_TICK_BASE];
+    h->dcd[c2] = g->dcd[c];
+  }
   HIPCHK(hipMemcpy2D(h->S.ds + c2, (size_t)8 * C2, ds.data(), 8, 8, DS_COUNT, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy2D(h->S.is + c2, (size_t)4 * C2, is.data(), 4, 4, IS_COUNT, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy2D(h->S.ls + c2, (size_t)8 * C2, ls.data(), 8, 8, LS_COUNT, hipMemcpyHostToDevice));
@@ -2317,9 +2376,9 @@ int aero_channel_export(aero_engine *e, const int *ch, int n, void *dst, size_t 
       h.hop_base = g->hop_base[c];
       h.soft_seen = g->soft_seen[c];
       h.pre_end = g->pre_end[c];
-      h.c_cd = g->c_cd[c];
-      h.c_dcd = g->c_dcd[c];
-      h.c_edges = g->c_edges[c];
+      h.c_cd = g->dcd[c].cd;
+      h.c_dcd = g->dcd[c].dcd;
+      h.c_edges = g->dcd[c].edges;
       h.msg_end = g->msg_end[c];
       h.infofield = g->infofield[c];
       h.save(o.host, g->host[c].get());
@@ -2447,9 +2506,13 @@ int aero_channel_import(aero_engine *e, const void *src, size_t bytes, int *ch_o
       g->hop_base[c] = h.hop_base;
       g->soft_seen[c] = h.soft_seen;
       g->pre_end[c] = h.pre_end;
-      g->c_cd[c] = h.c_cd;
-      g->c_dcd[c] = h.c_dcd;
-      g->c_edges[c] = h.c_edges;
+      g->dcd[c].cd = h.c_cd;
+      g->dcd[c].dcd = h.c_dcd;
+      g->dcd[c].edges = h.c_edges;
+      // the timer's running second travels in the slot (LS_TICK_BASE): its host mirror
+      if (g->dcd_cont && hipMemcpy(&g->tick_base[c], g->S.ls + (size_t)LS_TICK_BASE * g->C + c, sizeof(long long),
+                                   hipMemcpyDeviceToHost) != hipSuccess)
+        return undo(AERO_E_HIP);
       g->msg_end[c] = std::move(h.msg_end);
       g->infofield[c] = std::move(h.infofield);
       g->host[c] = std::move(h.host);
@@ -2858,9 +2921,14 @@ int aero_channel_get_events(aero_engine *e, int ch, aero_channel_events *out) {
   out->dcd_edges = pi[0];
   out->hunter_steps = pi[1];
   for (int k = 0; k < 8; k++) out->hunter_fc[k] = pd[k];
-  if (g->mode == MODE_C8400) {  // DecodeC's datacd follows the SU CRCs only (host, process_slot)
+  // The host keeps the countdown (dcd_host.h, process_slot) of the C channel,
+  // whose datacd follows the SU CRCs, and with AERO_F_DCD_TICK_CONT of continuous
+  // MSK too; with the flag every pass launched so far is handed over first
+  if (g->dcd_cont || g->mode == MODE_C8400) {
+    if (g->dcd_cont)
+      if (int rc = poll_slots(g, true)) return rc;
     host_wait(e);
-    out->dcd_edges = g->c_edges[c];
+    out->dcd_edges = g->dcd[c].edges;
   }
   return AERO_OK;
 }

@@ -235,6 +235,11 @@ enum LS : int {
   // the current message's first sample; the 52-bit shift registers of the
   // two dual-preamble detectors (real: r1, r2; imag: i1, i2, aerol.cpp:782-877)
   LS_PRE_END, LS_MSG_START, LS_C_R1, LS_C_R2, LS_C_I1, LS_C_I2,
+  // AERO_F_DCD_TICK_CONT (continuous MSK, C channel): the sample count at which
+  // the running second of AeroL's DCD timer began (zero at open, negative after
+  // an MSK rate change rescaled the elapsed part); the next tick fires once
+  // LS_NSAMP reaches LS_TICK_BASE + Fs, where a flagged demod launch ends
+  LS_TICK_BASE,
   LS_COUNT
 };
 
@@ -258,6 +263,7 @@ struct DevState {
   int C;                   // channel stride
   int mode;                // Mode
   int dcd_tick;            // AERO_F_DCD_TICK on a continuous OQPSK group
+  int dcd_cont;            // AERO_F_DCD_TICK_CONT on a continuous MSK or C group
   ModeGeom g;              // ring and block sizes of this group
   MskGen mg;               // generic-rate MSK groups: the rate's constants
   double *ds;              // [DS_COUNT][C]
@@ -294,7 +300,21 @@ struct DevState {
   double2 *csig;           // C channel: [C][C_FIR_SNZ] outputs of the last block transform (samples past its message)
   double2 *crem;           // C channel: [C][C_FIR_N - C_FIR_SNZ] JFastFir remainder
   int *err;                // [1] mapped pinned device-error word (DERR_*), sticky; read by the host
+  // AERO_F_DCD_TICK_CONT, MSK: [C] the pass's UW syncs per channel for the host's
+  // DCD countdown (mapped pinned, the job slot's): bits 0-3 their number, then 2
+  // bits each: the jobs the channel listed in this pass before that sync
+  unsigned long long *syncs;
 };
+
+// what a flagged demod launch does to the segment end (the host mirrors it,
+// engine.hip run_pass): a launch never runs past the sample that fires the
+// timer, so the tick lies between this pass's framing and the next one's.
+// `lim`: the samples the demod may consume (pushed; C: prefiltered)
+AERO_HD long long dcd_cont_end(long long end, long long base, int fs, long long boundary, long long lim) {
+  const long long t = base + fs;
+  return (t <= boundary && t <= lim) ? t : end;
+}
+constexpr int DCD_SYNC_MAX = 15;  // UW syncs of one channel a pass can report (32 bits apart, <= 216 bits a pass: 7)
 
 #if defined(__HIPCC__)
 // WaveTable's pointer wraps (DSP.h:59-65's loops) with their first iteration

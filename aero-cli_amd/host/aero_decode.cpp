@@ -351,9 +351,14 @@ int main(int argc, char **argv) {
   // DCD timer fires (decode/aerol.cpp:900-902): the engine runs it on the
   // sample clock (--burst: at the end of the message that completes a second,
   // AERO_F_DCD_TICK_BURST).  AERO_DCD_TICK=0 turns it off (the timer-less
-  // behaviour of a reference without an event loop; test support)
+  // behaviour of a reference without an event loop; test support);
+  // AERO_DCD_TICK=2 also runs it on continuous 600/1200-bps MSK and C channels
+  // (AERO_F_DCD_TICK_CONT): "Data carrier lost" then shows there too, and, as
+  // in the reference, a steady MSK carrier's DCD flaps
   const char *tick = getenv("AERO_DCD_TICK");
-  const int eflags = (tick && atoi(tick) == 0) ? 0 : (AERO_F_DCD_TICK | AERO_F_DCD_TICK_BURST);
+  const int tickv = tick ? atoi(tick) : 1;
+  const int eflags =
+      tickv == 0 ? 0 : (AERO_F_DCD_TICK | AERO_F_DCD_TICK_BURST | (tickv == 2 ? AERO_F_DCD_TICK_CONT : 0));
   aero_engine_cfg ecfg{dev ? atoi(dev) : 0, (int)topics.size(), eflags};
   if (int rc = aero_engine_create(&ecfg, &eng)) {
     AH_CRIT("Failed to create the MI355X demodulation engine: %s", aero_strerror(rc));

@@ -47,7 +47,10 @@ extern "C" {
                                   message a channel that has synced once searches
                                   for the UW only at the expected frame boundary.
                                   Continuous OQPSK only: burst channels ignore it
-                                  (AERO_F_DCD_TICK_BURST is theirs) */
+                                  (AERO_F_DCD_TICK_BURST is theirs), and so do
+                                  continuous MSK and C channels, whose
+                                  DataCarrierDetect then only ever rises
+                                  (AERO_F_DCD_TICK_CONT is theirs) */
 #define AERO_F_DCD_TICK_BURST 0x80 /* burst channels (10500 OQPSK, 600/1200 MSK): run
                                   the same timer.  A sync sets datacd and a countdown
                                   of 12 that only the timer takes down (the burst
@@ -71,6 +74,27 @@ extern "C" {
                                   (tests/oracle_tick.py).  Burst MSK does not gate
                                   its sync on datacd: there only the DataCarrierDetect
                                   changes differ */
+#define AERO_F_DCD_TICK_CONT 0x100 /* continuous 600/1200-bps MSK (any rate in
+                                  [12000, 96000] Hz) and the 8400-bps C channel: run
+                                  the same timer on the sample clock.  A channel
+                                  counts the samples until its next tick, starting
+                                  at the rate Fs it was opened at; the tick fires
+                                  after the sample that takes the count to 0 (after
+                                  everything that sample delivered to AeroL, before
+                                  anything the next one delivers) and the count
+                                  restarts at the current Fs.  An MSK rate change
+                                  Fs_old -> Fs_new rescales the elapsed part of the
+                                  second: left = Fs_new - ((Fs_old - left) * Fs_new)
+                                  / Fs_old in integers; AeroL's countdown, datacd and
+                                  the edge count carry over.  Neither framing reads
+                                  datacd, so every decoded output is the same with
+                                  and without the flag; only dcd_edges of
+                                  aero_channel_get_events differs: it can fall, which
+                                  is how a host sees a C call end or an MSK carrier
+                                  go (without the flag it rises once and stays).  As
+                                  in the reference, a steady MSK carrier's DCD flaps
+                                  under the timer.  OQPSK and burst channels ignore
+                                  the flag */
 
 typedef struct aero_engine aero_engine;
 
@@ -197,8 +221,13 @@ int aero_channel_export(aero_engine *e, const int *ch, int n, void *dst, size_t 
  * sizes, rows and fills of the per-channel arrays; not their offsets or the
  * group's size, which may differ), or whose decode-shaping flags differ from
  * the engine's (AERO_F_TRACE_PT, AERO_F_TRACE_BLOCKS, AERO_F_DCD_TICK,
- * AERO_F_DCD_TICK_BURST; the parity traces AERO_F_TRACE_SOFT and AERO_F_TRACE_HOPS are not checked, but
- * continue their numbering only between engines that both keep them).  Every
+ * AERO_F_DCD_TICK_BURST, AERO_F_DCD_TICK_CONT; the parity traces AERO_F_TRACE_SOFT and AERO_F_TRACE_HOPS are not checked, but
+ * continue their numbering only between engines that both keep them).  The
+ * fingerprint follows the library's state layout, not only its flags: the
+ * build that introduced AERO_F_DCD_TICK_CONT added one per-channel counter to
+ * every continuous kind (OQPSK, MSK and C, flag on or off), so blobs that an
+ * earlier build exported are refused by it and by later ones, a deliberate
+ * format break; burst blobs are not affected.  Every
  * length is checked before it is used.  A batch is all or nothing: on any
  * error no channel of it stays open.
  *

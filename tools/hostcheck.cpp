@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../aero-cli_amd/csrc/acars_host.h"
+#include "../aero-cli_amd/csrc/dcd_host.h"
 #include "../aero-cli_amd/csrc/tables_host.h"
 
 extern "C" {
@@ -40,6 +41,28 @@ size_t hc_save(void *h, uint8_t *dst, size_t cap) {
 }
 // PChannelHost::load: 1 when the state was taken, 0 when it was refused (h is then as a new host)
 int hc_load(void *h, const uint8_t *src, size_t n) { return static_cast<aero::PChannelHost *>(h)->load(src, n) ? 1 : 0; }
+
+// The host DCD countdown (dcd_host.h) over one pass of one channel, as
+// engine.hip process_slot walks it.  state: {countdown, datacd, edges}, updated.
+// syncs: the framing kernel's sync word; jobs: per listed job -1 (a block that
+// ends no frame) or the frame's SU count, its CRC-ok mask in masks; down: 3 / 5.
+void hc_dcd_pass(int *state, unsigned long long syncs, const int *jobs, const unsigned *masks, int njobs, int down,
+                 int tick) {
+  aero::DcdHost d;
+  d.cd = state[0];
+  d.dcd = state[1];
+  d.edges = state[2];
+  aero::DcdPass p;
+  p.syncs = syncs;
+  for (int j = 0; j < njobs; j++) {
+    p.job(d);
+    for (int k = 0; k < jobs[j]; k++) d.su((masks[j] >> k) & 1, down);
+  }
+  p.finish(d, tick != 0);
+  state[0] = d.cd;
+  state[1] = d.dcd;
+  state[2] = d.edges;
+}
 
 void hc_cis(double *cis) { aero::host_cis(cis); }
 void hc_twiddles(int nfft, double *tw, double *twi) { aero::host_twiddles(nfft, tw, twi); }
