@@ -39,6 +39,10 @@ MATH_FN = {'hypot': 0, 'atan2': 1, 'tanh': 2, 'sin': 3, 'cos': 4, 'log10': 5, 's
            'div': 8, 'div_c48000': 9, 'div_c360': 10, 'div_n': 11, 'div_c192000': 13, 'hypot_nr': 14, 'atan2_bf': 15,
            'tanh_bf': 16, 'sin_bf': 17, 'cos_bf': 18,
            'div_cw_wt': 19, 'set_phase_ptr': 20}
+# aero_device_viterbi variants (AERO_VIT_*) and the block length of the production-source ones
+VIT_VARIANT = {'wave': 0, 'regs': 1, 'regs2-self': 2, 'regs2-pair': 3, 'block4992': 4, 'block384': 5, 'block576': 6,
+               'csoft': 7}
+VIT_BLOCK = {'block4992': 4992, 'block384': 384, 'block576': 576, 'csoft': 5460}
 
 
 class EngineCfg(ctypes.Structure):
@@ -141,6 +145,8 @@ _SIGS = {
     'aero_sync': (ctypes.c_int, [ctypes.c_void_p]),
     'aero_device_math': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_size_t]),
+    'aero_device_viterbi': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     'aero_strerror': (ctypes.c_char_p, [ctypes.c_int]),
     # include/aero_chan.h
     'aero_chan_create': (ctypes.c_int, [ctypes.POINTER(ChanCfg), ctypes.POINTER(ChanMain), ctypes.c_int,
@@ -521,6 +527,23 @@ class Engine:
         _check(self.lib.aero_device_math(self.h, MATH_FN[fn], x.ctypes.data, y.ctypes.data, out.ctypes.data,
                                          x.size), 'aero_device_math')
         return out
+
+    def device_viterbi(self, variant, rows, nsoft=None):
+        """aero_device_viterbi (diagnostic): decodes the rows of a 2-D uint8
+        array with one of the device Viterbi decoders.  Flat variants: rows
+        are codewords, returns bits [ncw, nsoft / 2].  Production-source
+        variants: rows are records (block, 62 overlap bytes, first, pad) and
+        nsoft the stream length; returns (bits, overlap [ncw, 62])."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        assert rows.ndim == 2
+        src = variant in VIT_BLOCK
+        nsoft = rows.shape[1] if nsoft is None else int(nsoft)
+        bits = np.zeros((rows.shape[0], nsoft // 2), dtype=np.uint8)
+        ov = np.zeros((rows.shape[0], 62), dtype=np.uint8)
+        _check(self.lib.aero_device_viterbi(self.h, VIT_VARIANT[variant], rows.ctypes.data, rows.shape[0], nsoft,
+                                            bits.ctypes.data, ov.ctypes.data if src else None),
+               'aero_device_viterbi')
+        return (bits, ov) if src else bits
 
 
 # ------------------------------------------------------------------ channeliser

@@ -36,6 +36,7 @@
 
 #include "engine_common.h"
 #include "viterbi_dev.h"
+#include "viterbi_src.h"
 
 namespace aero {
 
@@ -393,27 +394,7 @@ void viterbi_read_stamps(unsigned long long *out) {
 #endif
 }
 
-// soft value p of a job's decoder input: the 62 overlap values of the
-// previous block (lane p's ovr), then the block deinterleaved on the fly
-// (deinterleave_ba, decode/aerol.cpp:594-613: position j * 64 + l comes from
-// row (27 l) mod 64, column j), then erasures (128)
-template <int BLK>
-struct BlockSoft {
-  const uint8_t *blk;
-  int ov, ovr;
-  // called by every lane; may_ov (wave-uniform): p may be an overlap position
-  __device__ __forceinline__ int get(int p, bool may_ov) const {
-    const int q = p - ov;
-    int v = 128;
-    if (q >= 0 && q < BLK) v = blk[(((q & 63) * 27) & 63) * (BLK / 64) + (q >> 6)];
-    if (may_ov) {
-      const int o = __builtin_amdgcn_ds_bpermute((p & 63) << 2, ovr);
-      if (q < 0) v = o;
-    }
-    return v;
-  }
-};
-
+// BlockSoft<BLK>, a job's decoder input read straight from the block: viterbi_src.h
 template <int BLK, int DL2>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void viterbi_kernel(DevState S, DevTables T, int trace) {
   constexpr int NL = BLK / 64, HALF = BLK / 2;

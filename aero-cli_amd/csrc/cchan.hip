@@ -40,6 +40,7 @@
 #include "engine_common.h"
 #include "fft_dit.h"
 #include "viterbi_dev.h"
+#include "viterbi_src.h"
 
 namespace aero {
 
@@ -674,25 +675,7 @@ __global__ __launch_bounds__(256) void frame_c_kernel(DevState S, int nch) {
   ls[LS_C_I2 * C + c] = (long long)i2;
 }
 
-namespace {
-// soft value p of a C job's decoder input: the previous frame's last 62
-// depunctured values, the 5460 depunctured ones (erasures at 4k + 3), 24 erasures
-struct CSoft {
-  const uint8_t *blk;
-  int ov, ovr;
-  __device__ __forceinline__ int get(int p, bool may_ov) const {
-    const int qq = p - ov;
-    int v = 128;
-    if (qq >= 0 && qq < C_BLOCK && (qq & 3) != 3) v = blk[qq];
-    if (may_ov) {
-      const int o = __builtin_amdgcn_ds_bpermute((p & 63) << 2, ovr);
-      if (qq < 0) v = o;
-    }
-    return v;
-  }
-};
-}  // namespace
-
+// CSoft, a C job's decoder input read straight from the frame: viterbi_src.h
 __global__ __launch_bounds__(64) void viterbi_c_kernel(DevState S, DevTables T) {
   constexpr int NW = (62 + C_BLOCK + 24) / 2 / 64 + 1;
   __shared__ uint64_t obits[NW];

@@ -47,6 +47,7 @@
 #include "slot_copy.h"
 #include "slot_reset.h"
 #include "tables_host.h"
+#include "viterbi_probe.h"
 
 namespace aero {
 void launch_demod(hipStream_t, const DevState &, const DevTables &, int, int, bool, bool);
@@ -2969,6 +2970,35 @@ int aero_device_math(aero_engine *e, int fn, const double *x, const double *y, d
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipMemcpy(out, d + 2 * n, n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipFree(d));
+  return AERO_OK;
+}
+
+int aero_device_viterbi(aero_engine *e, int variant, const uint8_t *in, size_t ncw, size_t nsoft, uint8_t *bits,
+                        uint8_t *overlap) {
+  if (!e || !in || !bits || ncw < 1 || ncw > (size_t)VP_MAX_CW) return AERO_E_INVALID;
+  const int blk = viterbi_probe_block(variant);
+  if (blk < 0) return AERO_E_INVALID;
+  size_t rec = nsoft;
+  if (blk == 0) {  // as long as the shortest stream with a full tail, at most an R/T block
+    if (nsoft % 2 || nsoft < 24 || nsoft > (size_t)VP_MAX_NSOFT) return AERO_E_INVALID;
+  } else {
+    if (!overlap || (nsoft != (size_t)blk + 24 && nsoft != (size_t)blk + 86)) return AERO_E_INVALID;
+    rec = (size_t)blk + 64;
+    for (size_t k = 0; k < ncw; k++)  // every record's flag says what the length says
+      if (in[k * rec + blk + 62] != (nsoft == (size_t)blk + 24 ? 1 : 0)) return AERO_E_INVALID;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  hipStream_t st = nullptr;
+  const size_t nin = ncw * rec, nbits = ncw * (nsoft / 2), nov = ncw * 62;
+  uint8_t *d = nullptr;
+  HIPCHK(hipMalloc(&d, nin + nbits + nov + 64));
+  HIPCHK(hipMemcpy(d, in, nin, hipMemcpyHostToDevice));
+  launch_viterbi_probe(st, variant, d, (int)ncw, (int)nsoft, d + nin, d + nin + nbits);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(bits, d + nin, nbits, hipMemcpyDeviceToHost));
+  if (blk) HIPCHK(hipMemcpy(overlap, d + nin + nbits, nov, hipMemcpyDeviceToHost));
   HIPCHK(hipFree(d));
   return AERO_OK;
 }

@@ -6,6 +6,10 @@
 // traceback leaving 35 columns of depth, zero tail with the last 6 steps
 // restricted to the states the tail can still reach, and a final traceback
 // from state 0. Shared by aerol.hip (framing blocks) and burst.hip (R/T tests).
+// viterbi_decode_wave, the plain form the two register decoders below restate,
+// is compiled into the diagnostic probe only (viterbi_probe.hip) and tested
+// through it; all three are compared with the oracle bit for bit on noisy,
+// tied and erased input (tests/test_gpu_viterbi.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -395,6 +395,44 @@ int aero_sync(aero_engine *e);
  * 8 division x/y.  x, y, out are host arrays. */
 int aero_device_math(aero_engine *e, int fn, const double *x, const double *y, double *out, size_t n);
 
+/* Diagnostic, like aero_device_math: runs one of the device's K=7 soft
+ * Viterbi decoders on ncw codewords of nsoft soft values each (parity test
+ * against the oracle on input no stream produces).  bits takes nsoft / 2
+ * bytes (0 / 1) per codeword: the nsoft / 2 - 6 decoded bits, then zeros.
+ * in, bits and overlap are host arrays; ncw <= 65536.
+ *
+ * Flat variants: `in` is ncw x nsoft soft values in decoding order, nsoft
+ * even, 24 <= nsoft <= 6080; overlap is not used.
+ *   AERO_VIT_WAVE        history in LDS
+ *   AERO_VIT_REGS        history in registers (the R/T tests' decoder)
+ *   AERO_VIT_REGS2_SELF  the two-codeword decoder given one codeword twice
+ *                        (a continuous job without a partner)
+ *   AERO_VIT_REGS2_PAIR  codewords 2k and 2k + 1 in one wave
+ * Production-source variants: the two-codeword decoder reads its stream as
+ * the continuous channels' kernels do.  `in` is ncw records of BLK + 64
+ * bytes: the raw block as the framing kernel stores it (BLK bytes: a 64-row
+ * interleaver block row by row, or the C channel's depunctured frame), the 62
+ * soft values the previous block's decode left as overlap, one byte `first`
+ * (1: the stream's first block, the overlap is not read), one pad byte.  The
+ * decoded stream is the overlap (unless first), the deinterleaved block
+ * (position 64 j + l from row (27 l) mod 64, column j; for C the frame with
+ * erasures at 4 k + 3) and 24 erasures, so nsoft = BLK + 24 (first) or
+ * BLK + 86 and every record's `first` agrees with it.  overlap takes the 62
+ * values per record the source hands to the next block.  Blocks 2k and
+ * 2k + 1 share a wave, as two channels' jobs do; C frames decode alone.
+ *   AERO_VIT_BLOCK4992 (OQPSK), AERO_VIT_BLOCK384 (MSK 600),
+ *   AERO_VIT_BLOCK576 (MSK 1200), AERO_VIT_CSOFT (BLK = 5460) */
+#define AERO_VIT_WAVE 0
+#define AERO_VIT_REGS 1
+#define AERO_VIT_REGS2_SELF 2
+#define AERO_VIT_REGS2_PAIR 3
+#define AERO_VIT_BLOCK4992 4
+#define AERO_VIT_BLOCK384 5
+#define AERO_VIT_BLOCK576 6
+#define AERO_VIT_CSOFT 7
+int aero_device_viterbi(aero_engine *e, int variant, const uint8_t *in, size_t ncw, size_t nsoft, uint8_t *bits,
+                        uint8_t *overlap);
+
 const char *aero_strerror(int rc);
 
 #ifdef __cplusplus

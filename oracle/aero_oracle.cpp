@@ -770,7 +770,12 @@ struct Viterbi {
       }
     }
   };
-  size_t decode_soft(const uint8_t *soft, size_t num_encoded_bits, uint8_t *msg) const {
+  // mut != 0 breaks one rule on purpose (oracle_viterbi_decode_soft_mut: proves
+  // that a test input reaches the rule; no decoding path passes it):
+  // 1 ACS ties keep the predecessor with dropped bit 1, 2 search ties go to
+  // the highest index, 3 no renormalisation subtract, 4 the windowed
+  // traceback starts from state 0, 5 the search in the tail is not restricted
+  size_t decode_soft(const uint8_t *soft, size_t num_encoded_bits, uint8_t *msg, int mut = 0) const {
     const unsigned cap = 5 * order + 15 * order;  // 140
     const unsigned min_tb = 5 * order;            // 35
     const unsigned renorm_interval = 65535u / (rate * 255u);
@@ -787,7 +792,7 @@ struct Viterbi {
       unsigned best = 0;
       uint16_t least = 0xFFFF;
       for (unsigned s = 0; s < nstates; s += skip)
-        if (d[s] < least) {
+        if (mut == 2 ? d[s] <= least : d[s] < least) {
           least = d[s];
           best = s;
         }
@@ -818,12 +823,12 @@ struct Viterbi {
       len++;
       if (renorm_counter == renorm_interval) {
         renorm_counter = 0;
-        unsigned m = search(d, skip);
+        unsigned m = search(d, mut == 5 ? 1 : skip);
         uint16_t mind = d[m];
-        for (unsigned s = 0; s < nstates; s++) d[s] = (uint16_t)(d[s] - mind);
-        if (len == cap) traceback(m, min_tb);
+        for (unsigned s = 0; s < nstates; s++) d[s] = (uint16_t)(d[s] - (mut == 3 ? 0 : mind));
+        if (len == cap) traceback(mut == 4 ? 0 : m, min_tb);
       } else if (len == cap) {
-        traceback(search(d, skip), min_tb);
+        traceback(mut == 4 ? 0 : search(d, mut == 5 ? 1 : skip), min_tb);
       }
     };
     // warmup (no history)
@@ -843,7 +848,7 @@ struct Viterbi {
         unsigned p0 = s >> 1, p1 = (s >> 1) | 32;
         uint16_t e0 = (uint16_t)(rd[p0] + dist[table[s]]);
         uint16_t e1 = (uint16_t)(rd[p1] + dist[table[s | 64]]);
-        if (e0 <= e1) {
+        if (mut == 1 ? e0 < e1 : e0 <= e1) {
           wr[s] = e0;
           h[s] = 0;
         } else {
@@ -864,7 +869,7 @@ struct Viterbi {
         unsigned p0 = s >> 1, p1 = (s >> 1) | 32;
         uint16_t e0 = (uint16_t)(rd[p0] + dist[table[s]]);
         uint16_t e1 = (uint16_t)(rd[p1] + dist[table[s | 64]]);
-        if (e0 <= e1) {
+        if (mut == 1 ? e0 < e1 : e0 <= e1) {
           wr[s] = e0;
           h[s] = 0;
         } else {
@@ -3399,6 +3404,9 @@ size_t oracle_conv_encode(const uint8_t *msg, size_t msg_len, uint8_t *encoded) 
 }
 size_t oracle_viterbi_decode_soft(const uint8_t *soft, size_t num_encoded_bits, uint8_t *msg) {
   return viterbi().decode_soft(soft, num_encoded_bits, msg);
+}
+size_t oracle_viterbi_decode_soft_mut(const uint8_t *soft, size_t num_encoded_bits, uint8_t *msg, int mut) {
+  return viterbi().decode_soft(soft, num_encoded_bits, msg, mut);
 }
 uint16_t oracle_crc16_bytes(const uint8_t *bytes, int n) {
   return crc16_bytes((const char *)bytes, n);

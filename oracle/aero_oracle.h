@@ -84,6 +84,13 @@ size_t oracle_items(const oracle_chan *c, char *dst, size_t cap);
 size_t oracle_conv_encode(const uint8_t *msg, size_t msg_len, uint8_t *encoded);
 size_t oracle_viterbi_decode_soft(const uint8_t *soft, size_t num_encoded_bits,
                                   uint8_t *msg);
+/* The same decoder with one rule broken (test infrastructure: shows that a
+ * test's inputs reach the rule).  mut 0: none; 1: ACS ties keep the
+ * predecessor whose dropped bit is 1; 2: least-metric ties go to the highest
+ * index; 3: no renormalisation subtract; 4: the windowed traceback starts
+ * from state 0; 5: the least-metric search is not restricted in the tail. */
+size_t oracle_viterbi_decode_soft_mut(const uint8_t *soft, size_t num_encoded_bits,
+                                      uint8_t *msg, int mut);
 
 /* Known-answer helpers */
 uint16_t oracle_crc16_bytes(const uint8_t *bytes, int n);

@@ -180,6 +180,8 @@ class Oracle:
             L.oracle_conv_encode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
             L.oracle_viterbi_decode_soft.restype = ctypes.c_size_t
             L.oracle_viterbi_decode_soft.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+            L.oracle_viterbi_decode_soft_mut.restype = ctypes.c_size_t
+            L.oracle_viterbi_decode_soft_mut.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
             L.oracle_crc16_bytes.restype = ctypes.c_uint16
             L.oracle_crc16_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
             L.oracle_scrambler_bits.argtypes = [ctypes.c_void_p, ctypes.c_int]

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Are a file's demod kernels still the same instructions?
 
-Usage: isa_compare.py OLD.s NEW.s
+Usage: isa_compare.py OLD.s NEW.s [WORD]
 Both are `hipcc --cuda-device-only -S` outputs of one source file at two
 commits (the product build's flags, aero-cli_amd/build.py).  For every kernel
-of OLD whose name holds "demod", the kernel of NEW with the same name, or with
+of OLD whose name holds WORD ("demod" unless given, e.g. "viterbi"), the
+kernel of NEW with the same name, or with
 a trailing `false` template argument added (a kernel that became a template on
 a flag), is compared instruction by instruction, comments, directives and
 basic-block numbers aside.  Prints per kernel the instruction counts, the
@@ -33,10 +34,10 @@ def funcs(path):
     return out
 
 
-def main(old, new):
+def main(old, new, word='demod'):
     P, N = funcs(old), funcs(new)
     for pn, pv in sorted(P.items()):
-        if 'demod' not in pn:
+        if word not in pn:
             continue
         cands = [pn, pn.replace('EEEvNS_8DevState', 'ELb0EEEvNS_8DevState'), pn.replace('kernelENS', 'kernelILb0EEEvNS')]
         nv = next((N[c] for c in cands if c in N), None)
@@ -50,4 +51,4 @@ def main(old, new):
 
 
 if __name__ == '__main__':
-    main(*sys.argv[1:3])
+    main(*sys.argv[1:4])
