@@ -42,6 +42,7 @@ MATH_FN = {'hypot': 0, 'atan2': 1, 'tanh': 2, 'sin': 3, 'cos': 4, 'log10': 5, 's
 # aero_device_viterbi variants (AERO_VIT_*) and the block length of the production-source ones
 VIT_VARIANT = {'wave': 0, 'regs': 1, 'regs2-self': 2, 'regs2-pair': 3, 'block4992': 4, 'block384': 5, 'block576': 6,
                'csoft': 7}
+FFT_KIND = {'dit': 0, 'chain': 1}  # aero_device_fft kinds (AERO_FFT_*)
 VIT_BLOCK = {'block4992': 4992, 'block384': 384, 'block576': 576, 'csoft': 5460}
 
 
@@ -147,6 +148,10 @@ _SIGS = {
                                         ctypes.c_void_p, ctypes.c_size_t]),
     'aero_device_viterbi': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    'aero_device_fft': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t,
+                                                                                 ctypes.c_void_p]),
+    'aero_channel_coarse_y': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
     'aero_strerror': (ctypes.c_char_p, [ctypes.c_int]),
     # include/aero_chan.h
     'aero_chan_create': (ctypes.c_int, [ctypes.POINTER(ChanCfg), ctypes.POINTER(ChanMain), ctypes.c_int,
@@ -544,6 +549,31 @@ class Engine:
                                             bits.ctypes.data, ov.ctypes.data if src else None),
                'aero_device_viterbi')
         return (bits, ov) if src else bits
+
+    def device_fft(self, kind, records, inverse=False, depth=0, start=1, stop=0):
+        """aero_device_fft (diagnostic): the rows of a 2-D complex128 array
+        (4096, 8192 or 16384 values, natural order) through the device's
+        'dit' transform (inverse: the sum without 1/N) or the coarse
+        estimator's 'chain' at depth 1-3 with the bins start..stop zeroed
+        after the first transform; returns the transforms, natural order."""
+        records = np.ascontiguousarray(records, dtype=np.complex128)
+        assert records.ndim == 2
+        n = records.shape[1]
+        log2n = n.bit_length() - 1 if n > 0 and n & (n - 1) == 0 else 0
+        out = np.empty_like(records)
+        _check(self.lib.aero_device_fft(self.h, FFT_KIND.get(kind, -1), log2n, int(inverse), int(depth), int(start),
+                                        int(stop), records.ctypes.data, records.shape[0], out.ctypes.data),
+               'aero_device_fft')
+        return out
+
+    def channel_coarse_y(self, ch):
+        """aero_channel_coarse_y: (first_bin, y[first_bin : first_bin + n]) of
+        the coarse estimator's smoothed spectrum as the next hop reads it."""
+        y = np.empty(16384, dtype=np.float64)
+        n, first = ctypes.c_size_t(), ctypes.c_int()
+        _check(self.lib.aero_channel_coarse_y(self.h, ch, y.ctypes.data, y.size, ctypes.byref(n), ctypes.byref(first)),
+               'aero_channel_coarse_y')
+        return int(first.value), y[:n.value].copy()
 
 
 # ------------------------------------------------------------------ channeliser

@@ -47,6 +47,7 @@
 #include "slot_copy.h"
 #include "slot_reset.h"
 #include "tables_host.h"
+#include "fft_probe.h"
 #include "viterbi_probe.h"
 
 namespace aero {
@@ -3000,6 +3001,66 @@ int aero_device_viterbi(aero_engine *e, int variant, const uint8_t *in, size_t n
   HIPCHK(hipMemcpy(bits, d + nin, nbits, hipMemcpyDeviceToHost));
   if (blk) HIPCHK(hipMemcpy(overlap, d + nin + nbits, nov, hipMemcpyDeviceToHost));
   HIPCHK(hipFree(d));
+  return AERO_OK;
+}
+
+int aero_device_fft(aero_engine *e, int kind, int log2n, int inverse, int depth, int start, int stop,
+                    const double *in, size_t nrec, double *out) {
+  if (!e || !in || !out || nrec < 1 || nrec > (size_t)FP_MAX_REC) return AERO_E_INVALID;
+  if (!fft_probe_known(kind, log2n, inverse, depth)) return AERO_E_INVALID;
+  const size_t nfft = (size_t)1 << log2n;
+  // the tables as group_create and the burst groups build them
+  std::vector<double> tw(2 * nfft), twi(2 * nfft), pg(2 * nfft, 0.0), pgi(2 * nfft, 0.0);
+  host_twiddles((int)nfft, tw.data(), twi.data());
+  if (kind == AERO_FFT_CHAIN) {
+    if (log2n == 14) {
+      fftl::twg_build<14>(tw.data(), pg.data());
+      fftl::twg_build<14>(twi.data(), pgi.data());
+    } else {
+      fftl::twg_build<13>(tw.data(), pg.data());
+      fftl::twg_build<13>(twi.data(), pgi.data());
+    }
+  }
+  HIPCHK(hipSetDevice(e->device));
+  hipStream_t st = nullptr;
+  const size_t tb = sizeof(double) * 2 * nfft, rb = nrec * tb;
+  char *d = nullptr;
+  HIPCHK(hipMalloc(&d, 4 * tb + 2 * rb));
+  const std::vector<double> *tabs[4] = {&tw, &twi, &pg, &pgi};
+  for (int k = 0; k < 4; k++) HIPCHK(hipMemcpy(d + k * tb, tabs[k]->data(), tb, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d + 4 * tb, in, rb, hipMemcpyHostToDevice));
+  auto tab = [&](int k) { return reinterpret_cast<const double2 *>(d + k * tb); };
+  launch_fft_probe(st, kind, log2n, inverse, depth, start, stop, reinterpret_cast<const double2 *>(d + 4 * tb),
+                   (int)nrec, reinterpret_cast<double2 *>(d + 4 * tb + rb), tab(0), tab(1), tab(2), tab(3));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(out, d + 4 * tb + rb, rb, hipMemcpyDeviceToHost));
+  HIPCHK(hipFree(d));
+  return AERO_OK;
+}
+
+int aero_channel_coarse_y(aero_engine *e, int ch, double *dst, size_t cap, size_t *n, int *first_bin) {
+  if (!e || !dst || !n || !first_bin) return AERO_E_INVALID;
+  if (route_burst(e, ch) >= 0) return AERO_E_INVALID;  // no coarse estimator in burst mode
+  int c;
+  Group *g = route(e, ch, c);
+  if (!g) return AERO_E_INVALID;
+  const size_t ylen = (size_t)(g->g.y_hi - g->g.y_lo + 1);
+  if (cap < ylen) return AERO_E_INVALID;
+  HIPCHK(hipSetDevice(e->device));
+  if (int rc = flush_pending_init(g)) return rc;
+  int yreset = 0;
+  HIPCHK(hipMemcpyAsync(g->pin_stat, g->S.is + (size_t)IS_YRESET * g->C + c, sizeof(int), hipMemcpyDeviceToHost,
+                        g->st));
+  HIPCHK(hipMemcpyAsync(dst, g->S.y + (size_t)c * ylen, ylen * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipStreamSynchronize(g->st));
+  memcpy(&yreset, g->pin_stat, sizeof yreset);
+  // bigchange() sets y = 20 at once; the kernel reads 20 for every bin at the
+  // next hop instead (coarse.hip yload) and leaves the row as it was until then
+  if (yreset)
+    for (size_t k = 0; k < ylen; k++) dst[k] = 20.0;
+  *n = ylen;
+  *first_bin = g->g.y_lo;
   return AERO_OK;
 }
 

@@ -433,6 +433,33 @@ int aero_device_math(aero_engine *e, int fn, const double *x, const double *y, d
 int aero_device_viterbi(aero_engine *e, int variant, const uint8_t *in, size_t ncw, size_t nsoft, uint8_t *bits,
                         uint8_t *overlap);
 
+/* Diagnostic, like aero_device_viterbi: runs a device FFT on nrec records of
+ * 2^log2n complex doubles (re, im pairs, natural order; host arrays) and
+ * returns each record's transform in natural order, one workgroup per record
+ * as in production, with tables built by the functions the channel groups
+ * use.  nrec <= 256.
+ *   AERO_FFT_DIT    fft_dit: log2n 12 or 13 (inverse 0 or 1) or 14 (inverse
+ *                   0).  The inverse is the plain sum, without JFFT's 1/N.
+ *                   depth, start and stop are not looked at.
+ *   AERO_FFT_CHAIN  the coarse estimator's chained transforms, log2n 13 or
+ *                   14, inverse 0: depth 1 the forward transform; depth 2
+ *                   then bins start..stop zeroed (none if start > stop) and
+ *                   the inverse (without 1/N); depth 3 then every value
+ *                   squared and the forward transform again.
+ * AERO_E_INVALID for anything else, before anything is launched. */
+#define AERO_FFT_DIT 0
+#define AERO_FFT_CHAIN 1
+int aero_device_fft(aero_engine *e, int kind, int log2n, int inverse, int depth, int start, int stop,
+                    const double *in, size_t nrec, double *out);
+
+/* Diagnostic: the coarse estimator's smoothed spectrum y of a continuous
+ * channel (CoarseFreqEstimate::y, decode/coarsefreqestimate.cpp) as its next
+ * hop will read it: the bins the engine keeps, *first_bin .. *first_bin + *n
+ * - 1 of the nfft, into dst (cap doubles; AERO_E_INVALID if too few).  After
+ * a bigchange() the kernel has not applied yet, 20.0 for every bin.  Waits
+ * for the channel's queued GPU work.  AERO_E_INVALID for a burst channel. */
+int aero_channel_coarse_y(aero_engine *e, int ch, double *dst, size_t cap, size_t *n, int *first_bin);
+
 const char *aero_strerror(int rc);
 
 #ifdef __cplusplus

@@ -3385,6 +3385,20 @@ size_t oracle_events(oracle_chan *c, long long *dcd_edges, double *fc, size_t ca
 size_t oracle_hops(const oracle_chan *c, double *dst, size_t cap_records) {
   return copy_out(c->hops(), dst, cap_records * 6) / 6;
 }
+static const Coarse *coarse_of(const oracle_chan *c) {
+  return c->oq ? &c->oq->coarse : (c->msk ? &c->msk->coarse : nullptr);
+}
+size_t oracle_coarse_y(const oracle_chan *c, double *dst, size_t cap) {
+  const Coarse *k = coarse_of(c);
+  return k ? copy_out(k->y, dst, cap) : 0;
+}
+size_t oracle_coarse_absx(const oracle_chan *c, double *dst, size_t cap) {
+  const Coarse *k = coarse_of(c);
+  if (!k) return 0;
+  std::vector<double> a(k->out.size());
+  for (size_t i = 0; i < a.size(); i++) a[i] = std::abs(k->out[i]);
+  return copy_out(a, dst, cap);
+}
 size_t oracle_pt(const oracle_chan *c, double *dst, size_t cap_records) {
   return copy_out(c->pts(), dst, cap_records * 2) / 2;
 }

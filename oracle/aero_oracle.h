@@ -61,6 +61,13 @@ size_t oracle_voice(const oracle_chan *c, uint8_t *dst, size_t cap);
  * mixer2 freq, mixer_center freq (after the slot ran), mse, signal flag. */
 size_t oracle_hops(const oracle_chan *c, double *dst, size_t cap_records);
 
+/* Continuous channels: CoarseFreqEstimate's smoothed spectrum y (all nfft
+ * values, fftshifted bin order), and |out[i]| of the last process() after its
+ * fftshift (the argument of its log10; before the first hop all zero).  Both
+ * return nfft and copy at most cap values. */
+size_t oracle_coarse_y(const oracle_chan *c, double *dst, size_t cap);
+size_t oracle_coarse_absx(const oracle_chan *c, double *dst, size_t cap);
+
 /* Decoder status events (decode/decode.cpp:429-439): *dcd_edges = the data
  * carrier detect changes SignalHunter::handleDcd passes on; returns the
  * number of newFreqCenter emissions and copies their centres (at most cap). */

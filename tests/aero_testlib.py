@@ -173,7 +173,7 @@ class Oracle:
             for f in ('oracle_softbits', 'oracle_blocks', 'oracle_frames', 'oracle_items'):
                 getattr(L, f).restype = ctypes.c_size_t
                 getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-            for f in ('oracle_hops', 'oracle_pt'):
+            for f in ('oracle_hops', 'oracle_pt', 'oracle_coarse_y', 'oracle_coarse_absx'):
                 getattr(L, f).restype = ctypes.c_size_t
                 getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
             L.oracle_conv_encode.restype = ctypes.c_size_t
@@ -258,6 +258,14 @@ class Oracle:
 
     def hops(self):
         return self._get(self.L.oracle_hops, np.float64, 6)
+
+    def coarse_y(self):
+        """all nfft values of CoarseFreqEstimate's smoothed spectrum y"""
+        return self._get(self.L.oracle_coarse_y, np.float64)
+
+    def coarse_absx(self):
+        """|out[i]| of the last coarse process() after its fftshift (log10's argument)"""
+        return self._get(self.L.oracle_coarse_absx, np.float64)
 
     def pt(self):
         return self._get(self.L.oracle_pt, np.float64, 2)

@@ -208,6 +208,35 @@ def test_export_is_a_snapshot(engine_lib, move_refs, kind):
     B.close()
 
 
+@pytest.mark.parametrize('kind', ['oqpsk', 'msk600', 'c8400'])
+def test_y_travels_with_the_channel(engine_lib, move_refs, kind):
+    """The coarse estimator's smoothed spectrum (aero_channel_coarse_y) read on
+    the importing engine, in another slot of a group with another pitch,
+    equals by bit pattern what the source read before the export."""
+    import aero_engine as ae
+    K = cc._kinds()[kind]
+    m = move_refs[kind]['a'][1]
+    A = ae.Engine(max_channels=64, flags=K['flags'])
+    B = ae.Engine(max_channels=128, flags=K['flags'])
+    assert A.open_channel(**K['open']) == 0
+    assert [B.open_channel(**K['open']) for _ in range(3)] == [0, 1, 2]
+    for r in range(min(12, _split(kind, m))):
+        A.push(0, m[r])
+        A.run()
+    first, y = A.channel_coarse_y(0)
+    assert y.max() > 20 and len(np.unique(y)) > 100, 'the channel has a history to carry'
+    ch = B.import_channel(A.export_channel(0))
+    assert ch == 3
+    first_b, y_b = B.channel_coarse_y(ch)
+    assert first_b == first and np.array_equal(y_b.view(np.int64), y.view(np.int64))
+    _, y_res = B.channel_coarse_y(0)
+    assert not y_res.any(), "a resident's row is untouched"
+    with pytest.raises(ae.AeroError):
+        B.channel_coarse_y(4)  # no such channel
+    A.close()
+    B.close()
+
+
 BATCH_MOVED = [4, 1, 7, 2]  # not in slot order: neighbours, a lone slot, the last one
 
 

@@ -7,11 +7,14 @@ gathers go out under the log10 loop, s_tw is written again before the fold's
 barrier, and the channel starts with the mix, without the plain head's two
 barriers.  AERO_COARSE_OVERLAP=0 gives every channel the plain head.
 
-Nothing may change by a bit: hop records (the y history, the ring image and
-its fix-up, zero_before, the fold and the hop control behind them), soft bits
-and items equal the CPU oracle's with the overlap on and off, in every
-adjacency of overlapped and plain heads, across a batch boundary, for the C
-channel's instance and with both instances in one engine."""
+Nothing may change by a bit: hop records (the ring image and its fix-up,
+zero_before, the fold's argmax and the hop control behind them), soft bits,
+items and the final smoothed spectrum y (aero_channel_coarse_y) equal the CPU
+oracle's with the overlap on and off, in every adjacency of overlapped and
+plain heads, across a batch boundary, for the C channel's instance and with
+both instances in one engine.  (Hop records alone do not pin the y history
+down: they hold the argmax of its fold.  y after every hop, on input that is
+not a clean carrier, is tests/test_gpu_coarse_y.py.)"""
 import concurrent.futures as cf
 
 import numpy as np
@@ -34,7 +37,7 @@ HOP = 4096
 def _oracle(pcm, bitrate=10500):
     o = tl.Oracle(bitrate=bitrate)
     o.push_chunked(pcm, 12000)
-    return o.softbits(), o.hops(), (o.c_units() if bitrate == 8400 else o.item_lines('A'))
+    return o.softbits(), o.hops(), (o.c_units() if bitrate == 8400 else o.item_lines('A')), o.coarse_y()
 
 
 def _oracles(streams, bitrate=10500):
@@ -86,8 +89,10 @@ def _chunk_rounds(streams, chunks):
 
 
 def _check(eng, chans, refs, what, units=False):
-    for k, (ch, (rsb, rh, rit)) in enumerate(zip(chans, refs)):
+    for k, (ch, (rsb, rh, rit, ry)) in enumerate(zip(chans, refs)):
         assert _same(eng.hops(ch), rh), '%s: channel %d hop records differ' % (what, k)
+        first, y = eng.channel_coarse_y(ch)
+        assert _same(y, ry[first:first + len(y)]), '%s: channel %d final y differs' % (what, k)
         assert np.array_equal(eng.softbits(ch), rsb), '%s: channel %d soft bits differ' % (what, k)
         if units:
             assert np.array_equal(eng.c_units(ch), rit), '%s: channel %d Call_progress SUs differ' % (what, k)
@@ -189,10 +194,12 @@ def test_batch_boundary(engine_lib, sixty_six, monkeypatch):
     streams, refs = sixty_six
     _env(monkeypatch, 1, 1)
     eng, chans = _run_rounds(ae, streams, _chunk_rounds(streams, [12000] * 66))
-    for k, (ch, (rsb, rh, _)) in enumerate(zip(chans, refs)):
+    for k, (ch, (rsb, rh, _, ry)) in enumerate(zip(chans, refs)):
         assert len(rh) >= int(1.5 * 48000) // HOP - 1
         assert _same(eng.hops(ch), rh), 'channel %d hop records differ' % k
         assert np.array_equal(eng.softbits(ch), rsb), 'channel %d soft bits differ' % k
+        first, y = eng.channel_coarse_y(ch)
+        assert _same(y, ry[first:first + len(y)]), 'channel %d final y differs' % k
     eng.close()
 
 

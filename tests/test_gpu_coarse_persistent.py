@@ -4,8 +4,9 @@ several channels.
 The 16384-point kinds launch at most AERO_COARSE_GRID workgroups (default:
 the device's CU count), each taking channels b, b + grid, ... (coarse_sched.h),
 so a handful of channels loop once the grid is set below their number.  The
-walk must not change a bit: hop records (the y history, the ring image, the
-fold and the hop control behind them), soft bits and items equal the CPU
+walk must not change a bit: hop records (the ring image, the fold's argmax and
+the hop control behind them), soft bits, items and the final smoothed
+spectrum y (aero_channel_coarse_y) equal the CPU
 oracle's (decode/coarsefreqestimate.cpp:89-150,
 decode/oqpskdemodulator.cpp:562-620) whatever the grid is."""
 import concurrent.futures as cf
@@ -31,7 +32,7 @@ SECONDS = 8.0
 def _oracle(pcm, bitrate=10500):
     o = tl.Oracle(bitrate=bitrate)
     o.push_chunked(pcm, 12000)
-    return o.softbits(), o.hops(), (o.c_units() if bitrate == 8400 else o.item_lines('A'))
+    return o.softbits(), o.hops(), (o.c_units() if bitrate == 8400 else o.item_lines('A')), o.coarse_y()
 
 
 def _oracles(streams, bitrate=10500):
@@ -61,7 +62,7 @@ def _run(ae, streams, chunks, flags, bitrate=10500):
 
 
 def _outputs(eng, chans):
-    out = [(eng.softbits(ch), eng.hops(ch), eng.items(ch)) for ch in chans]
+    out = [(eng.softbits(ch), eng.hops(ch), eng.items(ch), eng.channel_coarse_y(ch)) for ch in chans]
     eng.close()
     return out
 
@@ -90,9 +91,10 @@ def five_by_grid(engine_lib, five):
 def test_looping_uneven_split_out_of_step(five, five_by_grid):
     _, refs = five
     got = five_by_grid[2]
-    for k, ((sb, h, items), (rsb, rh, ritems)) in enumerate(zip(got, refs)):
+    for k, ((sb, h, items, (first, y)), (rsb, rh, ritems, ry)) in enumerate(zip(got, refs)):
         assert len(rh) >= int(SECONDS * 48000) // 4096 - 1
         assert _same(h, rh), 'channel %d hop records differ' % k
+        assert _same(y, ry[first:first + len(y)]), 'channel %d final y differs' % k
         assert np.array_equal(sb, rsb), 'channel %d soft bits differ' % k
         assert items == ritems, 'channel %d items differ' % k
     assert len(refs[0][0]) > 1000 and refs[0][2], 'oracle did not lock on the plain channel'
@@ -106,6 +108,7 @@ def test_grid_independence(five_by_grid):
             assert _same(a[1], b[1]), 'grid %d channel %d hop records differ' % (grid, k)
             assert np.array_equal(a[0], b[0]), 'grid %d channel %d soft bits differ' % (grid, k)
             assert a[2] == b[2]
+            assert a[3][0] == b[3][0] and _same(a[3][1], b[3][1]), 'grid %d channel %d final y differs' % (grid, k)
 
 
 def test_c_channel_loops(engine_lib, monkeypatch):
@@ -116,8 +119,10 @@ def test_c_channel_loops(engine_lib, monkeypatch):
     refs = _oracles(streams, 8400)
     eng, chans = _run(ae, streams, [12000] * 3, ae.F_TRACE_SOFT | ae.F_TRACE_HOPS, bitrate=8400)
     for k, ch in enumerate(chans):
-        rsb, rh, rcu = refs[k]
+        rsb, rh, rcu, ry = refs[k]
         assert len(rh) > 80 and _same(eng.hops(ch), rh), 'channel %d hop records differ' % k
+        first, y = eng.channel_coarse_y(ch)
+        assert _same(y, ry[first:first + len(y)]), 'channel %d final y differs' % k
         assert np.array_equal(eng.softbits(ch), rsb), 'channel %d soft bits differ' % k
         assert np.array_equal(eng.c_units(ch), rcu), 'channel %d Call_progress SUs differ' % k
     eng.close()

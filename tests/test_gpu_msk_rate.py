@@ -125,6 +125,35 @@ def test_msk_generic_rates_match_oracle(engine_lib, msk_kernel):
     eng.close()
 
 
+def test_y_survives_rate_changes(engine_lib):
+    """The smoothed spectrum y over 12000 -> 24000 -> 22050 Hz: the oracle's
+    y.resize keeps the values across setSettings and the engine copies the
+    channel's row into the new group (a fixed-rate one, then a generic one).
+    y by bit pattern after every message, hop records at the end."""
+    import aero_engine as ae
+    msgs = _messages(600, [(12000, 3.0, 0xE500, 1800.0, 14.0), (24000, 1.0, 0xE501, 1800.0, 14.0),
+                           (22050, 1.5, 0xE502, 1800.0, 14.0)], 0.25)
+    eng = ae.Engine(max_channels=2, flags=ae.F_TRACE_HOPS)
+    ch = eng.open_channel(600)
+    o = tl.Oracle(bitrate=600)
+    seen = set()
+    for k, (pcm, fs) in enumerate(msgs):
+        eng.push(ch, pcm, fs=fs)
+        eng.run()
+        o.push(pcm, fs=fs)
+        first, y = eng.channel_coarse_y(ch)
+        ry = o.coarse_y()[first:first + len(y)]
+        assert np.array_equal(y.view(np.int64), ry.view(np.int64)), 'y differs after message %d (%d Hz)' % (k, fs)
+        if fs not in seen:  # the first message at a rate: the row just moved, and it holds a history
+            seen.add(fs)
+            assert k == 0 or y.max() > 20
+    assert seen == {12000, 24000, 22050}
+    eng.flush()
+    h, rh = eng.hops(ch), o.hops()
+    assert len(rh) > 30 and h.shape == rh.shape and np.array_equal(h.view(np.int64), rh.view(np.int64))
+    eng.close()
+
+
 def test_msk_unsupported_rate_refused(engine_lib):
     import aero_engine as ae
     eng = ae.Engine(max_channels=2)

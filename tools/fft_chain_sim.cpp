@@ -140,23 +140,28 @@ struct Sim {
 
   int bin(int t, int i) const { return athr<L, K_G, false>(t) | areg(lay_g<L>(), L, i); }
 
-  void run(const C *in, int start, int stop, C *out) {
+  // depth 1: the forward transform alone; 2: boxcar and inverse as well; 3: all
+  void run(const C *in, int start, int stop, C *out, int depth = 3) {
     for (int t = 0; t < T; t++)  // START of the first transform: a = i | t << 4, sample bitrev(a)
       for (int i = 0; i < 16; i++) at(t, i) = in[brev32((uint32_t)(i | (t << 4))) >> (32 - L)];
     fft<true, false>();
-    for (int t = 0; t < T; t++)
-      for (int i = 0; i < 16; i++) {
-        const int k = bin(t, i);
-        if (k >= start && k <= stop) at(t, i) = C{0.0, 0.0};
-      }
-    fft<false, true>();
-    for (int t = 0; t < T; t++)
-      for (int i = 0; i < 16; i++) {
-        C &z = at(t, i);
-        const double r = z.x * z.x - z.y * z.y, im = 2.0 * (z.x * z.y);
-        z = C{r, im};
-      }
-    fft<false, false>();
+    if (depth >= 2) {
+      for (int t = 0; t < T; t++)
+        for (int i = 0; i < 16; i++) {
+          const int k = bin(t, i);
+          if (k >= start && k <= stop) at(t, i) = C{0.0, 0.0};
+        }
+      fft<false, true>();
+    }
+    if (depth >= 3) {
+      for (int t = 0; t < T; t++)
+        for (int i = 0; i < 16; i++) {
+          C &z = at(t, i);
+          const double r = z.x * z.x - z.y * z.y, im = 2.0 * (z.x * z.y);
+          z = C{r, im};
+        }
+      fft<false, false>();
+    }
     for (int t = 0; t < T; t++)
       for (int i = 0; i < 16; i++) out[bin(t, i)] = at(t, i);
   }
@@ -164,19 +169,29 @@ struct Sim {
 
 }  // namespace
 
+namespace {
+template <int L>
+int run_records(const double *tw, const double *twi, const double *in, int nrec, int start, int stop, int depth,
+                double *out) {
+  Sim<L> s;
+  s.set_tables(reinterpret_cast<const C *>(tw), reinterpret_cast<const C *>(twi));
+  for (int r = 0; r < nrec; r++)
+    s.run(reinterpret_cast<const C *>(in) + (size_t)r * Sim<L>::N, start, stop,
+          reinterpret_cast<C *>(out) + (size_t)r * Sim<L>::N, depth);
+  return 0;
+}
+}  // namespace
+
+// nrec records of 2^L values through the first `depth` (1..3) transforms of the chain
+extern "C" int fft_chain_sim_depth(int L, const double *tw, const double *twi, const double *in, int nrec, int start,
+                                   int stop, int depth, double *out) {
+  if (depth < 1 || depth > 3 || nrec < 0) return -1;
+  if (L == 14) return run_records<14>(tw, twi, in, nrec, start, stop, depth, out);
+  if (L == 13) return run_records<13>(tw, twi, in, nrec, start, stop, depth, out);
+  return -1;
+}
+
 extern "C" int fft_chain_sim(int L, const double *tw, const double *twi, const double *in, int start, int stop,
                              double *out) {
-  if (L == 14) {
-    Sim<14> s;
-    s.set_tables(reinterpret_cast<const C *>(tw), reinterpret_cast<const C *>(twi));
-    s.run(reinterpret_cast<const C *>(in), start, stop, reinterpret_cast<C *>(out));
-    return 0;
-  }
-  if (L == 13) {
-    Sim<13> s;
-    s.set_tables(reinterpret_cast<const C *>(tw), reinterpret_cast<const C *>(twi));
-    s.run(reinterpret_cast<const C *>(in), start, stop, reinterpret_cast<C *>(out));
-    return 0;
-  }
-  return -1;
+  return fft_chain_sim_depth(L, tw, twi, in, 1, start, stop, 3, out);
 }
