@@ -175,6 +175,21 @@ def build_hostcheck(out=HOSTCHECK_SO, extra=()):
     return out
 
 
+HOSTFUZZ = os.path.join(ROOT, 'tools', 'hostfuzz')
+
+
+def build_hostfuzz(out=HOSTFUZZ):
+    """tools/hostfuzz: the stand-alone AddressSanitizer + UBSan replay of a corpus of
+    tests/test_host_su_fuzz.py through PChannelHost (tools/hostfuzz_main.cpp); a program
+    of its own, run by hand, not a test."""
+    srcs = [os.path.join(ROOT, 'tools', 'hostfuzz_main.cpp'), os.path.join(CSRC, 'acars_host.cpp'),
+            os.path.join(CSRC, 'chan_blob.cpp')]
+    if _stale(out, srcs + [os.path.join(CSRC, h) for h in ('acars_host.h', 'chan_blob.h')]):
+        _run(['g++', '-O1', '-g', '-std=c++17', '-Wall', '-fsanitize=address,undefined',
+              '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer'] + FP + ['-o', out] + srcs)
+    return out
+
+
 def build_oracle():
     _run(['make', '-s', '-C', ORACLE_DIR])
     # the reference's own Qt-free sources (JFFT, Oscillator) as a second
@@ -356,12 +371,16 @@ if __name__ == '__main__':
     ap.add_argument('--synth', action='store_true')
     ap.add_argument('--oracle', action='store_true')
     ap.add_argument('--host', action='store_true')
+    ap.add_argument('--hostfuzz', action='store_true', help='tools/hostfuzz, the sanitizer replay of a host fuzz corpus')
     ap.add_argument('--asan', action='store_true', help='sanitizer builds into build/asan (tests/asan_check.sh)')
     ap.add_argument('--variants', default='', help='comma list of timing builds: drop, blibm, coarse, stamps')
     ap.add_argument('-j', type=int, default=4)
     a = ap.parse_args()
     for v in filter(None, a.variants.split(',')):
         print({'drop': build_drop, 'blibm': build_blibm, 'coarse': build_coarse, 'stamps': build_stamps}[v](a.j))
+    if a.hostfuzz:
+        print(build_hostfuzz())
+        sys.exit(0)
     if a.asan:
         print(build_asan(a.j))
         sys.exit(0)

@@ -96,7 +96,10 @@ bool PChannelHost::isu_update(const uint8_t *d, bool &missing) {
   IsuItem &it = isuitems_[idx];
   it.seqno--;
   if (it.seqno == 0) {
-    for (int i = 2; i <= it.nooct + 1; i++) it.userdata += (char)d[i];
+    // nooct is 4 bits: an ISU that said 9..15 is completed here when a later 0x71 of the same
+    // AES / GES has left a nooct <= 8 behind.  `data` is the SU's 10 bytes (infofield.mid(k * 12, 10))
+    // and reading a Qt 5 QByteArray past its end gives 0 (QByteRef), not the CRC or the next SU
+    for (int i = 2; i <= it.nooct + 1; i++) it.userdata += i < 10 ? (char)d[i] : '\0';
     lastvalid_ = it;
     return true;
   }

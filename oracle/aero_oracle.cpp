@@ -917,6 +917,17 @@ const Viterbi &viterbi() {
 }
 
 /* ---------------------------------------------------- ISU / ACARS parsing */
+// oracle_branch_hits: the returns of ISUData::update, ParserISU::parse,
+// ACARSDefragmenter::defragment and RISUData::update, and the SU dispatch of
+// AeroL::Decode's end-of-frame loop
+enum {
+  BR_ISU_NEW, BR_ISU_REPLACED, BR_SSU_MISSING, BR_SSU_LAST, BR_SSU_MORE, BR_PARSE_AES0, BR_PARSE_REG_PARITY,
+  BR_PARSE_TEXT_PARITY, BR_PARSE_ACARS, BR_PARSE_NONACARS, BR_DEFRAG_ALONE, BR_DEFRAG_STORED, BR_DEFRAG_GROWN,
+  BR_DEFRAG_JOINED, BR_DEFRAG_EXPIRED, BR_RISU_DONE, BR_RISU_WAITS, BR_RISU_SIGNALLING, BR_RISU_GROWS,
+  BR_RISU_EXPIRED, BR_SU_11, BR_SU_31, BR_SU_32, BR_SU_33, BR_SU_34, BR_SU_21, BR_SU_71, BR_SU_SSU, BR_SU_OTHER,
+  BR_SU_CRC_BAD, BR_ISU_EXPIRED, BR_COUNT
+};
+
 struct ISUItem {
   uint32_t AESID = 0;
   uint8_t GESID = 0, QNO = 0, SEQNO = 0, REFNO = 0, NOOCTLESTINLASTSSU = 0;
@@ -951,6 +962,11 @@ struct ISUData {
   std::vector<ISUItem> isuitems;
   ISUItem anisuitem, lastvalidisuitem;
   bool missingssu = false;
+  // test infrastructure (oracle_branch_hits): which way each call went
+  long long *hits = nullptr;
+  void hit(int i) {
+    if (hits) hits[i]++;
+  }
   void reset() { isuitems.clear(); }
   int find71(const ISUItem &a) {
     if (a.NOOCTLESTINLASTSSU > 8) return -1;
@@ -975,6 +991,7 @@ struct ISUData {
       if (isuitems[i].count > 10) {
         isuitems.erase(isuitems.begin() + i);
         i--;
+        hit(BR_ISU_EXPIRED);
       }
     }
   }
@@ -996,6 +1013,7 @@ struct ISUData {
       anisuitem.userdata.clear();
       for (int i = 8; i <= 9; i++) anisuitem.userdata += data[i];
       int idx = find71(anisuitem);
+      hit(idx < 0 ? BR_ISU_NEW : BR_ISU_REPLACED);
       if (idx < 0)
         isuitems.push_back(anisuitem);
       else
@@ -1010,16 +1028,23 @@ struct ISUData {
     int idx = findC0(anisuitem);
     if (idx < 0) {
       missingssu = true;
+      hit(BR_SSU_MISSING);
       return false;
     }
     ISUItem *p = &isuitems[idx];
     p->SEQNO--;
     if (p->SEQNO == 0) {
-      for (int i = 2; i <= (p->NOOCTLESTINLASTSSU + 1); i++) p->userdata += data[i];
+      // NOOCTLESTINLASTSSU may be 9..15 (an ISU the find functions passed because a later 0x71
+      // left a smaller value in anisuitem): data has 10 bytes, and a Qt 5 QByteRef read past the
+      // end gives 0 (qbytearray.h QByteRef::operator char)
+      for (int i = 2; i <= (p->NOOCTLESTINLASTSSU + 1); i++)
+        p->userdata += i < (int)data.size() ? data[i] : '\0';
       lastvalidisuitem = *p;
+      hit(BR_SSU_LAST);
       return true;
     }
     for (int i = 2; i <= 9; i++) p->userdata += data[i];
+    hit(BR_SSU_MORE);
     return false;
   }
 };
@@ -1031,6 +1056,10 @@ struct Defrag {
     int count;
   };
   std::vector<Ext> exts;
+  long long *hits = nullptr;
+  void hit(int i) {
+    if (hits) hits[i]++;
+  }
   int find(const ACARSItem &a) {
     for (size_t idx = 0; idx < exts.size(); idx++) {
       const ACARSItem &p = exts[idx].item;
@@ -1050,10 +1079,12 @@ struct Defrag {
       if (exts[i].count > 30) {
         exts.erase(exts.begin() + i);
         i--;
+        hit(BR_DEFRAG_EXPIRED);
       }
     }
     int idx = find(a);
     if (idx < 0) {
+      hit(a.moretocome ? BR_DEFRAG_STORED : BR_DEFRAG_ALONE);
       if (!a.moretocome) return true;
       exts.push_back({a, 0});
       return false;
@@ -1063,6 +1094,7 @@ struct Defrag {
     o->item.BI = a.BI;
     o->item.message += a.message;
     o->item.moretocome = a.moretocome;
+    hit(a.moretocome ? BR_DEFRAG_GROWN : BR_DEFRAG_JOINED);
     if (a.moretocome) return false;
     a = o->item;
     exts.erase(exts.begin() + idx);
@@ -1101,6 +1133,10 @@ struct Parser {
   Defrag defrag;
   ACARSItem an;
   std::string *items = nullptr;
+  long long *hits = nullptr;
+  void hit(int i) {
+    if (hits) hits[i]++;
+  }
   void lookup_and_emit(const ACARSItem &in) {
     ACARSItem p = in;
     size_t i = 0;
@@ -1109,7 +1145,10 @@ struct Parser {
     emit_item(*items, 'A', p);
   }
   bool parse(const ISUItem &isu) {
-    if (isu.AESID == 0) return false;
+    if (isu.AESID == 0) {
+      hit(BR_PARSE_AES0);
+      return false;
+    }
     std::vector<int> parities;
     std::string textish;
     for (size_t i = 0; i < isu.userdata.size(); i++) {
@@ -1138,13 +1177,19 @@ struct Parser {
       if ((uint8_t)ud[ud.size() - 1 - 3] == 0x97) an.moretocome = true;
       for (int k = 4; k < 4 + 7; k++) {
         byte = (uint8_t)ud[k] & 0x7F;
-        if (!parities[k]) return false;
+        if (!parities[k]) {
+          hit(BR_PARSE_REG_PARITY);
+          return false;
+        }
         an.PLANEREG += (char)byte;
       }
       if (an.hastext) {
         for (int k = 16; k < (int)ud.size() - 1 - 3; k++) {
           byte = (uint8_t)ud[k] & 0x7F;
-          if (!parities[k]) return false;
+          if (!parities[k]) {
+            hit(BR_PARSE_TEXT_PARITY);
+            return false;
+          }
           if (byte == 0x7F)
             an.message += "<DEL>";
           else
@@ -1154,8 +1199,10 @@ struct Parser {
       an.valid = true;
       emit_item(*items, 'F', an);
       if (defrag.defragment(an)) lookup_and_emit(an);
+      hit(BR_PARSE_ACARS);
       return true;
     }
+    hit(BR_PARSE_NONACARS);
     an.clear();
     an.downlink = downlink;
     an.isuitem = isu;
@@ -1185,6 +1232,10 @@ struct RISUItem : ISUItem {
 struct RISUData {
   std::vector<RISUItem> isuitems;
   RISUItem anisuitem, lastvalidisuitem;
+  long long *hits = nullptr;
+  void hit(int i) {
+    if (hits) hits[i]++;
+  }
   int find(const RISUItem &a) {
     if (a.SUTYPE > 11) return -1;
     if (a.SUTYPE < 1) return -1;
@@ -1200,6 +1251,7 @@ struct RISUData {
       if (isuitems[i].count > 10) {
         isuitems.erase(isuitems.begin() + i);
         i--;
+        hit(BR_RISU_EXPIRED);
       }
     }
     int byte1 = (uint8_t)data[0], byte2 = (uint8_t)data[1], byte3 = (uint8_t)data[2];
@@ -1240,7 +1292,10 @@ struct RISUData {
       for (int i = 0 - 1 + 7; i < BytesInSU - 1 + 7; i++) {
         // Qt5 QByteRef grows the array on an out-of-range write (zero-filled here)
         const size_t at = (size_t)(i + 11 * SUindex + 1 - 7);
-        if (at >= p->userdata.size()) p->userdata.resize(at + 1, '\0');
+        if (at >= p->userdata.size()) {
+          p->userdata.resize(at + 1, '\0');
+          hit(BR_RISU_GROWS);
+        }
         p->userdata[at] = data[i];
       }
       p->filledarray |= (1 << SUindex);
@@ -1250,8 +1305,10 @@ struct RISUData {
         ((p->filledarray == 3) && (SUTotal == 2)) || ((p->filledarray == 1) && (SUTotal == 1))) {
       lastvalidisuitem = *p;
       isuitems.erase(isuitems.begin() + idx);
+      hit(SignalingInfoSU ? BR_RISU_SIGNALLING : BR_RISU_DONE);
       return true;
     }
+    hit(BR_RISU_WAITS);
     return false;
   }
 };
@@ -1473,6 +1530,22 @@ struct AeroL {
     else if (datacdcountdown < 0)
       datacdcountdown = 0;
     if (datacd && !datacdcountdown) set_dcd(false);
+    link(LK_TICK, cntr);
+  }
+  // Link-layer trace (test infrastructure, oracle_link_trace): per event four
+  // values: kind, soft bits AeroL::Decode has taken so far (the event's bit
+  // included), cntr before the event changed it, datacdcountdown after it.
+  // The events are the places of AeroL::Decode that move cntr or the
+  // countdown: the UW hit (decode/aerol.cpp:1995-2015), the frame-length wrap
+  // without one (:2017-2030), a full interleaver block going to the decoder
+  // (:1493-1507), the end of the frame's SU loop (:1522-1990), the timer slot
+  // (:1043-1058) and isudata.reset() at an off-position UW (:1997-2003).
+  enum { LK_SYNC = 1, LK_WRAP = 2, LK_BLOCK = 3, LK_FRAME = 4, LK_TICK = 5, LK_ISU_RESET = 6 };
+  std::vector<long long> link_trace;
+  long long bits_in = 0;
+  void link(int kind, int cntr_before) {
+    const long long rec[4] = {kind, bits_in, cntr_before, datacdcountdown};
+    link_trace.insert(link_trace.end(), rec, rec + 4);
   }
   std::vector<int> block;
   std::vector<int> perm;  // interleaverowdepermute
@@ -1770,10 +1843,20 @@ struct AeroL {
         snprintf(b, sizeof b, " 0x%02X", (uint8_t)su[j]);
         decline += b;
       }
+      if (crc_calc != crc_rec) isudata.hit(BR_SU_CRC_BAD);
       if (crc_calc == crc_rec) {
         okmask |= 1u << k;
         decline += " ";
         uint8_t message = (uint8_t)su[0];
+        isudata.hit(message == 0x11   ? BR_SU_11
+                    : message == 0x31 ? BR_SU_31
+                    : message == 0x32 ? BR_SU_32
+                    : message == 0x33 ? BR_SU_33
+                    : message == 0x34 ? BR_SU_34
+                    : message == 0x21 ? BR_SU_21
+                    : message == 0x71 ? BR_SU_71
+                    : (message & 0xC0) == 0xC0 ? BR_SU_SSU
+                                               : BR_SU_OTHER);
         switch (message) {
           case 0x11:
             decline += "Log_on_confirm";
@@ -1875,6 +1958,7 @@ struct AeroL {
         continue;
       }
       if (muw < 100000) muw++;
+      bits_in++;
       int gotsync;
       if (!useingOQPSK && burstmode) {
         // MSK burst: phase-invariant UW (tolerance 4) accepted only within
@@ -2007,17 +2091,27 @@ struct AeroL {
             } else
               ch >>= 1;
           }
-          if ((cntr - BitsInHeader) == (NumberOfBits - 1)) frame_done();
+          link(LK_BLOCK, cntr);
+          if ((cntr - BitsInHeader) == (NumberOfBits - 1)) {
+            frame_done();
+            link(LK_FRAME, cntr);
+          }
         }
       }
       if (gotsync) {
-        if (!burstmode && cntr + 1 != TotalNumberOfBits) isudata.reset();
+        const int at = cntr;
+        if (!burstmode && cntr + 1 != TotalNumberOfBits) {
+          isudata.reset();
+          link(LK_ISU_RESET, at);
+        }
         cntr = -1;
         set_dcd(true);
         datacdcountdown = 12;
         scr_pos = 0;
+        link(LK_SYNC, at);
       }
       if (cntr + 1 == TotalNumberOfBits) {
+        link(LK_WRAP, cntr);
         scr_pos = 0;
         cntr = -1;
         if (burstmode) {  // end of the burst window: stop this call (aerol.cpp:2018-2029)
@@ -3306,6 +3400,7 @@ struct oracle_chan {
   std::unique_ptr<BurstMsk> bm;
   std::vector<uint8_t> blocks, frames, rt_tests, rt_packets, c_units, voice;
   std::string items;
+  long long hits[BR_COUNT] = {0};
   AeroL &aerol() { return oq ? oq->aerol : (msk ? msk->aerol : (bq ? bq->aerol : bm->aerol)); }
   const std::vector<uint8_t> &soft() const {
     return oq ? oq->soft_out : (msk ? msk->soft_out : (bq ? bq->soft_out : bm->soft_out));
@@ -3344,6 +3439,7 @@ oracle_chan *oracle_create(int bitrate, int flags) {
   c->aerol().blocks_out = &c->blocks;
   c->aerol().frames_out = &c->frames;
   c->aerol().parser.items = &c->items;
+  c->aerol().isudata.hits = c->aerol().parser.hits = c->aerol().parser.defrag.hits = c->aerol().risudata.hits = c->hits;
   return c;
 }
 void oracle_destroy(oracle_chan *c) { delete c; }
@@ -3408,6 +3504,40 @@ size_t oracle_blocks(const oracle_chan *c, uint8_t *dst, size_t cap) {
 size_t oracle_frames(const oracle_chan *c, uint8_t *dst, size_t cap) {
   return copy_out(c->frames, dst, cap);
 }
+size_t oracle_branch_hits(const oracle_chan *c, long long *dst, size_t cap) {
+  for (size_t i = 0; i < cap && i < (size_t)BR_COUNT; i++) dst[i] = c->hits[i];
+  return BR_COUNT;
+}
+size_t oracle_link_trace(oracle_chan *c, long long *dst, size_t cap_records) {
+  return copy_out(c->aerol().link_trace, dst, cap_records * 4) / 4;
+}
+// The SU loop at the end of a P-channel frame (decode/aerol.cpp:1522-1990) on
+// the caller's information field, as AeroL::Decode runs it once the last
+// block is packed: CRCs, countdown, dispatch, ISU assembly, items and a frame
+// record.  formatid is what :1219-1228 took from the header a frame earlier.
+int oracle_feed_frame(oracle_chan *c, const uint8_t *info, int len, int formatid) {
+  if (len < 0 || len > 312) return -1;
+  AeroL &a = c->aerol();
+  a.infofield.assign((const char *)info, (size_t)len);
+  a.formatid = formatid;
+  a.frame_done();
+  return 0;
+}
+// The R / T branch behind an OK_R / OK_T test (decode/aerol.cpp:1253-1460) on
+// the caller's packet: kind 'R' (the 19 bytes RTChannelDeleaveFECScram packs,
+// aerol.h:789-795) or 'T' (6 header bytes and nsus SUs less the chopped last
+// byte, aerol.h:816-830).  Shorter packets than the reference can hand over
+// are refused (-1).
+int oracle_feed_rt_packet(oracle_chan *c, int kind, const uint8_t *info, int len, int nsus) {
+  AeroL &a = c->aerol();
+  if (kind == 'R' ? len < 17 : (nsus < 0 || len < 6 + 12 * nsus - 2)) return -1;
+  a.rt.infofield.assign((const char *)info, (size_t)len);
+  a.rt.numberofsus = nsus;
+  a.rt_result(kind == 'R' ? RTChannel::OK_R : RTChannel::OK_T);
+  return 0;
+}
+// isudata.reset() (decode/aerol.cpp:1997-2003: a UW away from the frame's end)
+void oracle_feed_isu_reset(oracle_chan *c) { c->aerol().isudata.reset(); }
 size_t oracle_items(const oracle_chan *c, char *dst, size_t cap) {
   size_t n = std::min(cap, c->items.size());
   if (dst && n) memcpy(dst, c->items.data(), n);

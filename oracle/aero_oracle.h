@@ -84,6 +84,28 @@ size_t oracle_blocks(const oracle_chan *c, uint8_t *dst, size_t cap);
  * then uint32 infofield length, then uint32 crc-ok bitmask (26 bits). */
 size_t oracle_frames(const oracle_chan *c, uint8_t *dst, size_t cap);
 
+/* Link-layer trace of AeroL::Decode (continuous P channels): per event four
+ * long long: kind (1 UW sync, 2 frame-length wrap without a UW, 3 block handed
+ * to the decoder, 4 frame done, 5 DCD tick, 6 isudata.reset()), soft bits taken
+ * so far, cntr before the event, datacdcountdown after it.  For the CPU tests
+ * to prove what a stream reaches; nothing of it is compared with the GPU. */
+size_t oracle_link_trace(oracle_chan *c, long long *dst, size_t cap_records);
+
+/* Past the modem: the end-of-frame SU loop on caller bytes (a frame record
+ * and items come out as from a decoded frame), the R/T branch on a caller's
+ * packet (kind 'R' / 'T'; -1: shorter than the reference can produce), and
+ * isudata.reset(). */
+int oracle_feed_frame(oracle_chan *c, const uint8_t *info, int len, int formatid);
+int oracle_feed_rt_packet(oracle_chan *c, int kind, const uint8_t *info, int len, int nsus);
+void oracle_feed_isu_reset(oracle_chan *c);
+
+/* How often each return of ISUData::update, ParserISU::parse,
+ * ACARSDefragmenter::defragment and RISUData::update and each branch of the
+ * end-of-frame SU dispatch was taken (the order of tests/aero_testlib.py
+ * BRANCHES); returns their number.  For a test to show that its inputs reach
+ * them all. */
+size_t oracle_branch_hits(const oracle_chan *c, long long *dst, size_t cap);
+
 /* ACARSItems as canonical text lines (see tests/aero_items.py). */
 size_t oracle_items(const oracle_chan *c, char *dst, size_t cap);
 

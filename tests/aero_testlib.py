@@ -82,6 +82,47 @@ def synth_msk(seconds=10.0, bitrate=600, seed=0xAE40, carrier=1800.0, ebn0=12.0,
     return pcm
 
 
+def synth_bits(bits, seed=0xAE20, carrier=12037.5, ebn0=12.0, amplitude=0.25, phase0=0.3, lead_in=1000, fs=48000.0,
+               tail=2000):
+    """int16 PCM of caller-made channel bits (0/1) as a 10500-bps OQPSK P
+    channel (aero_synth_p10500_bits: the modulator of synth()); `tail` samples
+    of noise follow the last bit."""
+    global _synth
+    if _synth is None:
+        _synth = ctypes.CDLL(SYNTH_SO)
+    _synth.aero_synth_p10500_bits.restype = ctypes.c_size_t
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    n = int(lead_in) + int(np.ceil(len(bits) * fs / 10500.0)) + int(tail)
+    pcm = np.zeros(n, dtype=np.int16)
+    cfg = SynthCfg(fs, carrier, phase0, amplitude, ebn0, seed, 0.0, lead_in)
+    took = _synth.aero_synth_p10500_bits(ctypes.byref(cfg), bits.ctypes.data_as(ctypes.c_void_p),
+                                         ctypes.c_size_t(len(bits)), pcm.ctypes.data_as(ctypes.c_void_p),
+                                         ctypes.c_size_t(n))
+    assert took == len(bits), 'the stream is too short for its bits'
+    return pcm
+
+
+def synth_msk_bits(bits, bitrate=600, baud=None, seed=0xAE40, carrier=1800.0, ebn0=12.0, amplitude=0.25, phase0=0.3,
+                   lead_in=500, fs=None, tail=1000):
+    """int16 PCM of caller-made channel bits as an MSK P channel at 12/24 kHz
+    (aero_synth_msk_bits: the modulator of synth_msk(), `baud` as there)."""
+    global _synth
+    if _synth is None:
+        _synth = ctypes.CDLL(SYNTH_SO)
+    _synth.aero_synth_msk_bits.restype = ctypes.c_size_t
+    fs = float(fs) if fs else (12000.0 if bitrate == 600 else 24000.0)
+    baud = baud or bitrate
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    n = int(lead_in) + int(np.ceil(len(bits) * fs / baud)) + int(tail)
+    pcm = np.zeros(n, dtype=np.int16)
+    cfg = SynthCfg(fs, carrier, phase0, amplitude, ebn0, seed, 0.0, lead_in)
+    took = _synth.aero_synth_msk_bits(ctypes.byref(cfg), ctypes.c_int(baud), bits.ctypes.data_as(ctypes.c_void_p),
+                                      ctypes.c_size_t(len(bits)), pcm.ctypes.data_as(ctypes.c_void_p),
+                                      ctypes.c_size_t(n))
+    assert took == len(bits), 'the stream is too short for its bits'
+    return pcm
+
+
 def synth_c(seconds=10.0, seed=0xAEC0, carrier=12000.0, ebn0=12.0, amplitude=0.25, phase0=0.3, lead_in=1000,
             return_frames=False):
     """int16 48 kHz PCM of an 8400-bps C channel (tools/aero_synth.cpp
@@ -198,6 +239,15 @@ class Oracle:
             L.oracle_events.restype = ctypes.c_size_t
             L.oracle_events.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.c_void_p,
                                         ctypes.c_size_t]
+            L.oracle_link_trace.restype = ctypes.c_size_t
+            L.oracle_link_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+            L.oracle_feed_frame.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]
+            L.oracle_feed_rt_packet.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
+                                                ctypes.c_int]
+            L.oracle_feed_isu_reset.argtypes = [ctypes.c_void_p]
+            L.oracle_feed_isu_reset.restype = None
+            L.oracle_branch_hits.restype = ctypes.c_size_t
+            L.oracle_branch_hits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
             cls._libs['L'] = L
         return cls._libs['L']
 
@@ -276,6 +326,30 @@ class Oracle:
     def frames(self):
         return self._get(self.L.oracle_frames, np.uint8)
 
+    def link_trace(self):
+        """[n, 4] int64 (kind, soft bits taken, cntr before, datacdcountdown
+        after) of every link-layer event; kinds LK_*"""
+        return self._get(self.L.oracle_link_trace, np.int64, 4)
+
+    def feed_frame(self, info, formatid=1):
+        """AeroL's end-of-frame SU loop on these bytes, past the modem"""
+        assert self.L.oracle_feed_frame(self.h, bytes(info), len(info), formatid) == 0
+
+    def feed_rt_packet(self, kind, info, nsus=0):
+        """the R/T branch on a packet; False: shorter than the reference can hand over"""
+        return self.L.oracle_feed_rt_packet(self.h, ord(kind), bytes(info), len(info), nsus) == 0
+
+    def feed_isu_reset(self):
+        self.L.oracle_feed_isu_reset(self.h)
+
+    def branch_hits(self):
+        """{branch name: times taken} (oracle_branch_hits)"""
+        n = self.L.oracle_branch_hits(self.h, None, 0)
+        assert n == len(BRANCHES)
+        v = np.zeros(n, dtype=np.int64)
+        self.L.oracle_branch_hits(self.h, v.ctypes.data, n)
+        return dict(zip(BRANCHES, (int(x) for x in v)))
+
     def events(self):
         """(dcd_edges, [centre of every SignalHunter step]) (decode/decode.cpp:429-439)"""
         e = ctypes.c_longlong()
@@ -290,6 +364,15 @@ class Oracle:
         self.L.oracle_items(self.h, b, n)
         lines = b.raw[:n].decode().splitlines()
         return [l for l in lines if l.startswith(kind + ' ')]
+
+
+# oracle/aero_oracle.cpp BR_*: the returns of the ISU / ACARS assembly and the SU dispatch
+BRANCHES = ('isu_new', 'isu_replaced', 'ssu_missing', 'ssu_last', 'ssu_more', 'parse_aes0', 'parse_reg_parity',
+            'parse_text_parity', 'parse_acars', 'parse_nonacars', 'defrag_alone', 'defrag_stored', 'defrag_grown',
+            'defrag_joined', 'defrag_expired', 'risu_done', 'risu_waits', 'risu_signalling', 'risu_grows',
+            'risu_expired', 'su_11', 'su_31', 'su_32', 'su_33', 'su_34', 'su_21', 'su_71', 'su_ssu', 'su_other',
+            'su_crc_bad', 'isu_expired')
+LK_SYNC, LK_WRAP, LK_BLOCK, LK_FRAME, LK_TICK, LK_ISU_RESET = 1, 2, 3, 4, 5, 6
 
 
 def frame_records(raw):

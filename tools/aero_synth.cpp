@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -42,6 +43,15 @@ size_t aero_synth_p10500(const aero_synth_cfg *cfg, int16_t *pcm, size_t nsample
 /* 600/1200-bps MSK P-channel (cfg->fs = 12000 / 24000); frames: 72 info bytes each */
 size_t aero_synth_msk(const aero_synth_cfg *cfg, int bitrate, int baud, int16_t *pcm, size_t nsamples,
                       uint8_t *frames, size_t frames_cap);
+/* The same two modulators over caller-made channel bits (one byte per bit,
+ * 0 / 1): the Q/I arm mapping and RRC pulse of aero_synth_p10500, the
+ * differential encoding and half-sine pulse of aero_synth_msk at `baud`.
+ * Behind the last bit the carrier is off (noise only).  Return the number of
+ * bits modulated into the nsamples. */
+size_t aero_synth_p10500_bits(const aero_synth_cfg *cfg, const uint8_t *bits, size_t nbits, int16_t *pcm,
+                              size_t nsamples);
+size_t aero_synth_msk_bits(const aero_synth_cfg *cfg, int baud, const uint8_t *bits, size_t nbits, int16_t *pcm,
+                           size_t nsamples);
 /* 8400-bps C channel; frames: 36 SU bytes + 300 voice bytes each */
 size_t aero_synth_c8400(const aero_synth_cfg *cfg, int16_t *pcm, size_t nsamples, uint8_t *frames,
                         size_t frames_cap);
@@ -279,11 +289,32 @@ double rrc1(double x) {
          (M_PI * x * (1 - 16 * a * a * x * x));
 }
 
-}  // namespace
+// Where a modulator gets its channel bits: appends the next ones (a frame, or
+// all the caller gave), false when there are none left
+typedef std::function<bool(std::vector<int> &)> BitSource;
 
-extern "C" size_t aero_synth_p10500(const aero_synth_cfg *cfg, int16_t *pcm, size_t nsamples,
-                                    uint8_t *frames, size_t frames_cap) {
-  Tx tx(*cfg);
+// a BitSource's bits one at a time; -1 behind the last
+struct BitFifo {
+  const BitSource &more;
+  std::vector<int> buf;
+  size_t rd = 0, taken = 0;
+  bool dry = false;
+  explicit BitFifo(const BitSource &m) : more(m) {}
+  int next() {
+    while (rd == buf.size() && !dry) {
+      buf.clear();
+      rd = 0;
+      if (!more(buf)) dry = true;
+    }
+    if (rd == buf.size()) return -1;
+    taken++;
+    return buf[rd++];
+  }
+};
+
+// OQPSK at 10500 bps: even channel bits on Q, odd on I, Q leading I by T/2,
+// RRC alpha = 1, real carrier, AWGN; returns the bits taken
+size_t modulate_oqpsk(const aero_synth_cfg *cfg, int16_t *pcm, size_t nsamples, const BitSource &more) {
   const double Fs = cfg->fs, Ts = Fs / 5250.0;  // samples per arm symbol
   const int SPAN = 8;                           // +- symbols
   const int OS = 256;                           // table oversampling
@@ -301,18 +332,14 @@ extern "C" size_t aero_synth_p10500(const aero_synth_cfg *cfg, int16_t *pcm, siz
     double f = p - ip;
     return tab[ip] * (1 - f) + tab[ip + 1] * f;
   };
-  // symbols: q[k] from chan bit 2k, i[k] from chan bit 2k+1, generated lazily
+  // symbols: q[k] from chan bit 2k, i[k] from chan bit 2k+1, generated lazily; 0 = carrier off
   std::vector<double> qs, is;
-  size_t nframes = 0;
+  BitFifo fifo(more);
   auto ensure = [&](size_t k) {
     while (qs.size() <= k) {
-      uint8_t *dst = (frames && nframes < frames_cap) ? frames + 312 * nframes : nullptr;
-      tx.next_frame(dst);
-      nframes++;
-      for (int b = 0; b < 5250; b += 2) {
-        qs.push_back(tx.chan[b] ? 1.0 : -1.0);
-        is.push_back(tx.chan[b + 1] ? 1.0 : -1.0);
-      }
+      const int q = fifo.next(), i = fifo.next();
+      qs.push_back(q < 0 ? 0.0 : (q ? 1.0 : -1.0));
+      is.push_back(i < 0 ? 0.0 : (i ? 1.0 : -1.0));
     }
   };
   // power: A^2 * (E[I^2]+E[Q^2]) / 2 ; E[I^2] = energy (unit symbols, 1 per period)
@@ -348,7 +375,7 @@ extern "C" size_t aero_synth_p10500(const aero_synth_cfg *cfg, int16_t *pcm, siz
     if (v < -32768) v = -32768;
     pcm[n] = (int16_t)v;
   }
-  return nframes;
+  return fifo.taken;
 }
 
 /* MSK: channel bits b_n are differentially encoded onto alternating arms so
@@ -357,28 +384,22 @@ extern "C" size_t aero_synth_p10500(const aero_synth_cfg *cfg, int16_t *pcm, siz
  * receiver reads first (imag) a 1 is a sign change, on the other a 1 is no
  * change.  Half-sine pulses over two bit periods (the receiver's matched
  * filter, mskdemodulator.cpp:126-133), arms offset by one bit period. */
-extern "C" size_t aero_synth_msk(const aero_synth_cfg *cfg, int bitrate, int baud, int16_t *pcm, size_t nsamples,
-                                 uint8_t *frames, size_t frames_cap) {
-  // bitrate selects the frame layout (N = 6 / 9), baud the modulation rate.
-  // aero-decode -b 1200 demodulates at fb = 600 (decode/decode.cpp:142-150
-  // never sets fb), so only 600-baud input exercises its 1200 framing.
-  Tx tx(*cfg);
-  const int N = bitrate == 600 ? 6 : 9;
+size_t modulate_msk(const aero_synth_cfg *cfg, int baud, int16_t *pcm, size_t nsamples, const BitSource &more) {
   const double Fs = cfg->fs, Tb = Fs / (double)baud;
-  std::vector<double> arm;  // +-1 per channel bit
-  size_t nframes = 0;
+  std::vector<double> arm;  // +-1 per channel bit; 0 = carrier off
+  BitFifo fifo(more);
   double last = 1.0;
   auto ensure = [&](size_t k) {
     while (arm.size() <= k) {
-      uint8_t *dst = (frames && nframes < frames_cap) ? frames + 72 * nframes : nullptr;
-      tx.next_frame_msk(N, dst);
-      nframes++;
-      for (int b = 0; b < 1200; b++) {
-        const size_t n = arm.size();
-        const bool flip = (n % 2 == 0) ? !tx.chan[b] : tx.chan[b];
-        last = flip ? -last : last;
-        arm.push_back(last);
+      const size_t n = arm.size();
+      const int bit = fifo.next();
+      if (bit < 0) {
+        arm.push_back(0.0);
+        continue;
       }
+      const bool flip = (n % 2 == 0) ? !bit : bit;
+      last = flip ? -last : last;
+      arm.push_back(last);
     }
   };
   const double A = cfg->amplitude;
@@ -416,7 +437,62 @@ extern "C" size_t aero_synth_msk(const aero_synth_cfg *cfg, int bitrate, int bau
     if (v < -32768) v = -32768;
     pcm[n] = (int16_t)v;
   }
+  return fifo.taken;
+}
+
+// the caller's bits, all at once
+BitSource given_bits(const uint8_t *bits, size_t nbits) {
+  bool done = false;
+  return [=](std::vector<int> &out) mutable {
+    if (done) return false;
+    done = true;
+    for (size_t i = 0; i < nbits; i++) out.push_back(bits[i] ? 1 : 0);
+    return nbits > 0;
+  };
+}
+
+}  // namespace
+
+extern "C" size_t aero_synth_p10500(const aero_synth_cfg *cfg, int16_t *pcm, size_t nsamples,
+                                    uint8_t *frames, size_t frames_cap) {
+  Tx tx(*cfg);
+  size_t nframes = 0;
+  modulate_oqpsk(cfg, pcm, nsamples, [&](std::vector<int> &out) {
+    uint8_t *dst = (frames && nframes < frames_cap) ? frames + 312 * nframes : nullptr;
+    tx.next_frame(dst);
+    nframes++;
+    out.insert(out.end(), tx.chan.begin(), tx.chan.end());
+    return true;
+  });
   return nframes;
+}
+
+extern "C" size_t aero_synth_p10500_bits(const aero_synth_cfg *cfg, const uint8_t *bits, size_t nbits, int16_t *pcm,
+                                         size_t nsamples) {
+  return modulate_oqpsk(cfg, pcm, nsamples, given_bits(bits, nbits));
+}
+
+extern "C" size_t aero_synth_msk(const aero_synth_cfg *cfg, int bitrate, int baud, int16_t *pcm, size_t nsamples,
+                                 uint8_t *frames, size_t frames_cap) {
+  // bitrate selects the frame layout (N = 6 / 9), baud the modulation rate.
+  // aero-decode -b 1200 demodulates at fb = 600 (decode/decode.cpp:142-150
+  // never sets fb), so only 600-baud input exercises its 1200 framing.
+  Tx tx(*cfg);
+  const int N = bitrate == 600 ? 6 : 9;
+  size_t nframes = 0;
+  modulate_msk(cfg, baud, pcm, nsamples, [&](std::vector<int> &out) {
+    uint8_t *dst = (frames && nframes < frames_cap) ? frames + 72 * nframes : nullptr;
+    tx.next_frame_msk(N, dst);
+    nframes++;
+    out.insert(out.end(), tx.chan.begin(), tx.chan.end());
+    return true;
+  });
+  return nframes;
+}
+
+extern "C" size_t aero_synth_msk_bits(const aero_synth_cfg *cfg, int baud, const uint8_t *bits, size_t nbits,
+                                      int16_t *pcm, size_t nsamples) {
+  return modulate_msk(cfg, baud, pcm, nsamples, given_bits(bits, nbits));
 }
 
 /* ------------------------------------------------------------------ bursts

@@ -24,6 +24,7 @@ void hc_frame(void *h, const uint8_t *info, int len, uint32_t okmask, int format
 void hc_rt_packet(void *h, int r_packet, const uint8_t *info, int len, int nsus) {
   static_cast<aero::PChannelHost *>(h)->rt_packet(r_packet != 0, info, len, nsus);
 }
+void hc_isu_reset(void *h) { static_cast<aero::PChannelHost *>(h)->isu_reset(); }
 // pops up to cap items (emission order); returns the number copied
 size_t hc_items(void *h, aero_acars_item *dst, size_t cap) {
   auto &v = static_cast<aero::PChannelHost *>(h)->items;
