@@ -188,7 +188,13 @@ AERO_HD double aero_hypot_nr(double x, double y) {
 #if defined(__HIP_DEVICE_COMPILE__)
   x = __builtin_fabs(x);
   y = __builtin_fabs(y);
-  const double ax = x < y ? y : x, ay = x < y ? x : y;
+  // the larger and the smaller of two non-negative finite values: what
+  // aero_hypot's compare and selects give, bit for bit (no -0 after fabs).
+  // By the instructions themselves: with __builtin_fmax / fmin the coarse
+  // kernel's 16384-point instances spilled 18-26 registers
+  double ax, ay;
+  asm("v_max_f64 %0, %1, %2" : "=v"(ax) : "v"(x), "v"(y));
+  asm("v_min_f64 %0, %1, %2" : "=v"(ay) : "v"(x), "v"(y));
   const double s = ax * ax + ay * ay;
   const double rs = __builtin_amdgcn_rsq(s);
   double g = s * rs, hh = rs * 0.5;
@@ -928,5 +934,75 @@ AERO_HD double aero_log10_tab(double x, const double *tab) {
   return z + y * AERO_G_LOG10_2HI;
 }
 AERO_HD double aero_log10(double x) { return aero_log10_tab(x, &aero_g_log_tab[0][0]); }
+
+/* aero_log10_tab for finite x >= 1 (the coarse estimator's max(|X|, 1)), the
+ * same FP operations in the same order, so the same bits.  There the wrapper
+ * takes none of its zero / negative / subnormal / NaN exits, its exponent
+ * k = (ix >> 52) - 1023 is >= 0 (so its i is 0 and log's argument is the
+ * mantissa m in [1, 2)), and in log itself m is a normal number whose
+ * k = (int64_t)tmp >> 52 is 0 or 1; everything integer fits the high word.
+ * In pieces:
+ *   g_log10_ge1_split   y = exponent, m = mantissa in [1, 2)
+ *   g_log10_ge1_near    whether log(m) takes the polynomial around 1
+ *   g_log_m_far / _near log(m) by the table path / by that polynomial
+ *   g_log10_ge1_join    the wrapper's last two lines */
+AERO_HD void g_log10_ge1_split(double x, double &y, double &m) {
+  const uint32_t hx = hiw(x);
+  y = (double)((int)(hx >> 20) - 1023);
+  m = sethi(x, (hx & 0x000fffffu) | 0x3ff00000u);
+}
+AERO_HD bool g_log10_ge1_near(double m) { return hiw(m) < 0x3ff10900u; }  // m < 1 + 0x1.09p-4 (log's HI)
+AERO_HD double g_log_m_near(double m) {
+  if (hiw(m) == 0x3ff00000u && low(m) == 0) return 0.0;
+  const double *B = aero_g_log_poly1;
+  const double r = m - 1.0;
+  const double r2 = r * r, r3 = r * r2;
+  double p9 = fma(r3, B[10], fma(r2, B[9], fma(r, B[8], B[7])));
+  p9 = fma(p9, r3, fma(r2, B[6], fma(r, B[5], B[4])));
+  const double p = fma(p9, r3, fma(r2, B[3], fma(r, B[2], B[1])));
+  const double rhi = fma(-AERO_G_TWO27, r, fma(r, AERO_G_TWO27, r));
+  const double rlo = r - rhi;
+  const double hi = fma(rhi * rhi, B[0], r);
+  double lo = fma(rhi * rhi, B[0], r - hi);
+  lo = fma(B[0] * rlo, r + rhi, lo);
+  return hi + fma(p, r3, lo);
+}
+AERO_HD double g_log_m_far(double m, const double *tab) {
+  const uint32_t hm = hiw(m);
+  const uint32_t tmp = hm - 0x3fe60000u;
+  const int i = (int)((tmp >> 13) & 127);
+  const uint32_t k = tmp >> 20;  // 0 or 1
+  const double z = sethi(m, hm - (k << 20));
+  const double invc = tab[2 * i], logc = tab[2 * i + 1];
+  const double r = fma(z, invc, -1.0);
+  const double kd = (double)(int)k;
+  const double w = fma(kd, AERO_G_LN2HI, logc);
+  const double hi = w + r;
+  const double lo = fma(kd, AERO_G_LN2LO, (w - hi) + r);
+  const double r2 = r * r;
+  const double *A = aero_g_log_poly;
+  const double q = fma(fma(r, A[4], A[3]), r2, fma(r, A[2], A[1]));
+  return fma(r * r2, q, fma(r2, A[0], lo)) + hi;
+}
+AERO_HD double g_log10_ge1_join(double y, double lg) {
+  const double z = y * AERO_G_LOG10_2LO + lg * AERO_G_IVLN10;
+  return z + y * AERO_G_LOG10_2HI;
+}
+AERO_HD double aero_log10_ge1_tab(double x, const double *tab) {
+  double y, m;
+  g_log10_ge1_split(x, y, m);
+  return g_log10_ge1_join(y, g_log10_ge1_near(m) ? g_log_m_near(m) : g_log_m_far(m, tab));
+}
+AERO_HD double aero_log10_ge1(double x) { return aero_log10_ge1_tab(x, &aero_g_log_tab[0][0]); }
+
+/* aero_log10_tab of an argument that is at least 1 (the caller's promise):
+ * aero_log10_ge1_tab when every active lane's argument is finite (one uniform
+ * branch), the general code otherwise */
+AERO_HD double aero_log10_ge1_w(double x, const double *tab) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (__builtin_expect(__all(hiw(x) < 0x7ff00000u), 1)) return aero_log10_ge1_tab(x, tab);
+#endif
+  return aero_log10_tab(x, tab);
+}
 
 }  // namespace aero

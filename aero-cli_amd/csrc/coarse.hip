@@ -40,13 +40,15 @@ namespace aero {
 #ifdef AERO_X_OCML  // timing experiment only (see demod_oqpsk.hip)
 #define CO_HYPOT ::hypot
 #define CO_HYPOT_NR ::hypot
-#define CO_LOG10 ::log10
-#define CO_LOG10_TAB(x, tab) ::log10(x)
+#define CO_LOG10_GE1(x) ::log10(x)
+#define CO_LOG10_GE1_TAB(x, tab) ::log10(x)
 #else
 #define CO_HYPOT aero_hypot
 #define CO_HYPOT_NR aero_hypot_nr
-#define CO_LOG10 aero_log10
-#define CO_LOG10_TAB(x, tab) aero_log10_tab(x, tab)
+// log10 of max(|X|, 1): the argument is at least 1, and finite for any finite
+// spectrum (one wave-uniform test; aero_math.h)
+#define CO_LOG10_GE1(x) aero_log10_ge1_w(x, &aero_g_log_tab[0][0])
+#define CO_LOG10_GE1_TAB(x, tab) aero_log10_ge1_w(x, tab)
 #endif
 
 // Geometry of one channel's coarse estimate (decode/coarsefreqestimate.cpp:39-76
@@ -507,14 +509,21 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(cs[i].x), "+v"(cs[i].y));
+        // entries below zero_before were cleared (AFC, CenterFreqChangedSlot);
+        // entries of samples before the channel's first are the ring's own
+        // contents (zero for a new channel: CIS[0] x 0; a channel that changed
+        // rate keeps the ring it had, mskdemodulator.cpp:94-218).  zero_before
+        // lies inside the snapshot only for the four hops after a reset or a
+        // centre-frequency step: on every other hop (one wave-uniform test,
+        // the same in all waves: HopPro) no element's sample number is looked at
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          // entries below zero_before were cleared (AFC, CenterFreqChangedSlot);
-          // entries of samples before the channel's first are the ring's own
-          // contents (zero for a new channel: CIS[0] x 0; a channel that changed
-          // rate keeps the ring it had, mskdemodulator.cpp:94-218)
-          const long long s = s0 + bitrev<L>(epos<L, 0>(t, i));
-          x[i] = s < zero_before ? make_double2(0.0, 0.0) : make_double2(cs[i].x * dval[i], cs[i].y * dval[i]);
+        for (int i = 0; i < 16; ++i) x[i] = make_double2(cs[i].x * dval[i], cs[i].y * dval[i]);
+        if (s0 < zero_before) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const long long s = s0 + bitrev<L>(epos<L, 0>(t, i));
+            if (s < zero_before) x[i] = make_double2(0.0, 0.0);
+          }
         }
         __syncthreads();  // the ring image is read: the LDS is the transforms' from here on
         CSTAMP(2);
@@ -624,9 +633,18 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       auto ypad = [](int q) { return fftl::ypadn<6>(q); };
       // |X| by aero_hypot_nr when every value of the wave is in its range (the
       // usual case: |X| of a live channel is ~1e9), else by aero_hypot
+      // (of the 16384-point kinds only the registers some lane stores are
+      // looked at: a register holds the FT bins from out_bin_reg(i) on, the
+      // lanes their low bits.  The 8192-point kinds spilled with that)
+      static_assert(fftl::thread_mask(fftl::lay_g<L>(), L) == FT - 1, "a register's bins are one run of FT");
+      auto stored = [](int i) {
+        const int y0 = chain::out_bin_reg<L>(i) ^ (N / 2);
+        return y0 + FT - 1 >= K::YLO && y0 <= K::YHI;
+      };
       bool nr = true;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
+        if (PERSIST && !stored(i)) continue;
         const double a = fabs(x[i].x), b = fabs(x[i].y);
         nr = nr && a <= 0x1p200 && b <= 0x1p200 && (a >= 0x1p-200 || b >= 0x1p-200);
       }
@@ -685,9 +703,9 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
         // in issue order) for every table gather issued before it
         double lg;
         if constexpr (OVL)
-          lg = CO_LOG10_TAB(fmax(ylds[ypad(k)], 1.0), sm.logtab);
+          lg = CO_LOG10_GE1_TAB(fmax(ylds[ypad(k)], 1.0), sm.logtab);
         else
-          lg = CO_LOG10(fmax(ylds[ypad(k)], 1.0));
+          lg = CO_LOG10_GE1(fmax(ylds[ypad(k)], 1.0));
         const double ynew = yold * 0.9 + 0.1 * 10 * lg;
         // OVL: to memory after the loop, from ylds (ystore below)
         if constexpr (!OVL) yg[k] = ynew;
@@ -782,7 +800,7 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
               asm volatile("" : "+v"(a));
               if constexpr (j + 3 < NIT) yp = yg[min(k + 3 * FT, YLEN - 1)];
 #endif
-              const double lg = CO_LOG10_TAB(fmax(ylds[ypad(in ? k : YLEN - 1)], 1.0), sm.logtab);
+              const double lg = CO_LOG10_GE1_TAB(fmax(ylds[ypad(in ? k : YLEN - 1)], 1.0), sm.logtab);
               const double ynew = a + 0.1 * 10 * lg;
               if (in) ylds[ypad(k)] = ynew;
             }
@@ -857,8 +875,8 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       CSTAMP(8);
       pre = OVL && nxt;
       if constexpr (OVL) {
-        // the overlapped head's serial rest: the successor's mix, by today's
-        // expression.  x[] holds the table entries gathered under the log10
+        // the overlapped head's serial rest: the successor's mix, by the plain
+        // head's expression.  x[] holds the table entries gathered under the log10
         // loop and the fold, pcmw[] the PCM halves.  Past the barrier above
         // the waves go straight into the successor's forward transform, with
         // neither of the plain head's barriers: s_tw is whole again since
@@ -871,8 +889,15 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
           for (int i = 0; i < 16; ++i) {
             const uint32_t pw = pcmw[i >> 1];
             const double dv = ((double)(int16_t)((i & 1) ? (pw >> 16) : (pw & 0xFFFFu))) / 32768.0;
-            const long long s = s0n + bitrev<L>(epos<L, 0>(t, i));
-            x[i] = s < pn.zero_before ? make_double2(0.0, 0.0) : make_double2(x[i].x * dv, x[i].y * dv);
+            x[i] = make_double2(x[i].x * dv, x[i].y * dv);
+          }
+          // zero_before inside the snapshot (rare, wave-uniform; see the plain head)
+          if (s0n < pn.zero_before) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              const long long s = s0n + bitrev<L>(epos<L, 0>(t, i));
+              if (s < pn.zero_before) x[i] = make_double2(0.0, 0.0);
+            }
           }
         }
         CSTAMP(2);

@@ -147,6 +147,8 @@ __global__ void math_kernel(int fn, const double *x, const double *y, double *ou
     case 18: { double sn, cs; aero_sincos_bf(a, sn, cs, aero_g_sincostab); r = cs; break; }
     case 19: r = div_cw(a, (double)WTSIZE); break;
     case 20: r = set_phase_ptr(a); break;
+    // a >= 1: as the coarse kernel calls it, behind the wave's finiteness test (tests/test_gpu_coarse_diet.py)
+    case 21: r = aero_log10_ge1_w(a, &aero_g_log_tab[0][0]); break;
     default: break;
   }
   out[i] = r;

@@ -392,7 +392,8 @@ int aero_sync(aero_engine *e);
 
 /* Evaluates the device libm on n inputs (parity test of aero_math.h):
  * fn 0 hypot, 1 atan2, 2 tanh, 3 sin, 4 cos, 5 log10, 6 sqrt, 7 fmod(x,360),
- * 8 division x/y.  x, y, out are host arrays. */
+ * 8 division x/y, ..., 21 log10 of x >= 1 (aero_engine.py MATH_FN has the
+ * whole list).  x, y, out are host arrays. */
 int aero_device_math(aero_engine *e, int fn, const double *x, const double *y, double *out, size_t n);
 
 /* Diagnostic, like aero_device_math: runs one of the device's K=7 soft

@@ -23,6 +23,7 @@ extern "C" void aero_math_host_eval(int fn, const double *x, const double *y, do
       case 9: { double s, c; aero::aero_sincos(a, s, c); r = s; break; }
       case 10: { double s, c; aero::aero_sincos(a, s, c); r = c; break; }
       case 12: r = aero::aero_log(a); break;
+      case 15: r = aero::aero_log10_ge1(a); break;  // finite a >= 1
       default: break;
     }
     out[i] = r;
