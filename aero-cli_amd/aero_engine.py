@@ -88,6 +88,19 @@ class ChanVfo(ctypes.Structure):
 CHAN_F_HOST_OUT = 0x1
 
 
+class ChanSurveyCfg(ctypes.Structure):
+    _fields_ = [('log2n', ctypes.c_int), ('window', ctypes.c_void_p)]
+
+
+class SurveyPeakCfg(ctypes.Structure):
+    _fields_ = [('threshold', ctypes.c_double), ('min_bins', ctypes.c_int), ('merge_gap', ctypes.c_int)]
+
+
+class SurveyPeak(ctypes.Structure):
+    _fields_ = [('offset_hz', ctypes.c_double), ('bandwidth_hz', ctypes.c_double), ('ratio', ctypes.c_double),
+                ('frequency', ctypes.c_longlong), ('first_bin', ctypes.c_int), ('last_bin', ctypes.c_int)]
+
+
 class ChannelEvents(ctypes.Structure):
     _fields_ = [('dcd_edges', ctypes.c_int64), ('hunter_steps', ctypes.c_int64), ('hunter_fc', ctypes.c_double * 8)]
 
@@ -177,6 +190,13 @@ _SIGS = {
     'aero_chan_vfo_count': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     'aero_chan_vfo_settle': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     'aero_chan_stat': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]),
+    'aero_chan_survey_start': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ChanSurveyCfg)]),
+    'aero_chan_survey_stop': (ctypes.c_int, [ctypes.c_void_p]),
+    'aero_chan_survey_read': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    'aero_survey_peaks': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
+                                         ctypes.POINTER(SurveyPeakCfg), ctypes.POINTER(SurveyPeak), ctypes.c_size_t,
+                                         ctypes.POINTER(ctypes.c_size_t)]),
 }
 
 _lib = None
@@ -784,7 +804,58 @@ class Channeliser:
         return int(n.value)
 
     def stat(self, name):
-        """aero_chan_stat: 'device_bytes', 'vfo_inits' (start-kernel launches) or 'slots_free'."""
+        """aero_chan_stat: 'device_bytes', 'vfo_inits' (start-kernel launches), 'slots_free',
+        'survey_launches' or 'survey_segments'."""
         v = ctypes.c_uint64()
         _check(self.lib.aero_chan_stat(self.h, name.encode(), ctypes.byref(v)), 'aero_chan_stat')
         return int(v.value)
+
+    # ---- wideband carrier survey (include/aero_chan.h)
+    def survey_start(self, log2n, window=None):
+        """Starts the averaged power spectrum of the input on segments of 2**log2n samples (12, 13
+        or 14), from the next read pushed.  window: None, 2**log2n float64 values, or 'hann'
+        (0.5 - 0.5 cos(2 pi i / N), built with numpy: a convenience, nothing exact rests on it)."""
+        n = 1 << int(log2n)
+        if isinstance(window, str):
+            if window != 'hann':
+                raise ValueError('unknown window %r' % window)
+            window = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)
+        if window is not None:
+            window = np.ascontiguousarray(window, dtype=np.float64)
+            if window.shape != (n,):
+                raise ValueError('the window holds %d values' % n)
+        cfg = ChanSurveyCfg(int(log2n), window.ctypes.data if window is not None else None)
+        _check(self.lib.aero_chan_survey_start(self.h, ctypes.byref(cfg)), 'aero_chan_survey_start')
+        self._survey_n = n
+
+    def survey_stop(self):
+        _check(self.lib.aero_chan_survey_stop(self.h), 'aero_chan_survey_stop')
+
+    def survey_read(self, reset=False):
+        """(summed power per bin as float64[N], natural bin order; segments summed), after the runs
+        launched so far; reset=True then zeroes both (the segment grid goes on)."""
+        out = np.zeros(getattr(self, '_survey_n', 1 << 14), dtype=np.float64)
+        seg = ctypes.c_uint64()
+        _check(self.lib.aero_chan_survey_read(self.h, out.ctypes.data, out.size, ctypes.byref(seg), int(bool(reset))),
+               'aero_chan_survey_read')
+        return out, int(seg.value)
+
+
+def survey_peaks(power, log2n, sample_rate, center, mix_offset=0, threshold=8.0, min_bins=2, merge_gap=2):
+    """aero_survey_peaks (host only, no GPU): the carriers in a survey spectrum as dicts with
+    offset_hz, bandwidth_hz, ratio, frequency (what a [vfos] entry's frequency takes to be centred
+    on the carrier), first_bin and last_bin, in ascending frequency."""
+    lib = load_library()
+    power = np.ascontiguousarray(power, dtype=np.float64)
+    if power.shape != (1 << int(log2n),):
+        raise ValueError('the spectrum holds %d values' % (1 << int(log2n)))
+    cfg = SurveyPeakCfg(float(threshold), int(min_bins), int(merge_gap))
+    n = ctypes.c_size_t()
+    args = (power.ctypes.data, int(log2n), int(sample_rate), int(center), int(mix_offset), ctypes.byref(cfg))
+    rc = lib.aero_survey_peaks(*args, None, 0, ctypes.byref(n))
+    if rc not in (AERO_OK, AERO_E_FULL):
+        raise AeroError(rc, 'aero_survey_peaks')
+    out = (SurveyPeak * max(1, n.value))()
+    _check(lib.aero_survey_peaks(*args, out, n.value, ctypes.byref(n)), 'aero_survey_peaks')
+    return [dict(offset_hz=p.offset_hz, bandwidth_hz=p.bandwidth_hz, ratio=p.ratio, frequency=int(p.frequency),
+                 first_bin=p.first_bin, last_bin=p.last_bin) for p in out[:n.value]]

@@ -32,8 +32,8 @@ CXX_FLAGS = ['-O2', '-std=c++17', '-fPIC', '-Wall'] + FP
 
 HIP_SRCS = ['demod_oqpsk.hip', 'demod_msk.hip', 'coarse.hip', 'aerol.hip', 'engine.hip', 'chan.hip', 'burst.hip', 'burst_msk.hip',
             'burst_engine.hip', 'cchan.hip', 'slot_reset.hip', 'slot_copy.hip', 'viterbi_probe.hip',
-            'fft_probe.hip']
-CXX_SRCS = ['tables_host.cpp', 'acars_host.cpp', 'chan_blob.cpp']
+            'fft_probe.hip', 'survey.hip']
+CXX_SRCS = ['tables_host.cpp', 'acars_host.cpp', 'chan_blob.cpp', 'survey_host.cpp']
 # Per-file codegen: the burst demodulators' loops hold their state in
 # registers; LLVM's machine LICM hoists every FP64 constant of the inlined
 # libm ports out of the loop into SGPRs, hundreds of them, which then spill

@@ -47,6 +47,7 @@
 #include "../../include/aero_chan.h"
 #include "chan_slots.h"
 #include "engine_internal.h"
+#include "survey.h"
 #include "tables_host.h"
 
 using aero::host_pub_hilbert;
@@ -376,6 +377,9 @@ struct aero_chan {
   size_t cap_nv = 0;  // VFOs d_jobs / d_start are sized for
   size_t dev_bytes = 0;
   uint64_t vfo_inits = 0;
+  // wideband carrier survey (survey.hip): nullptr while none is on
+  aero::Survey *survey = nullptr;
+  uint64_t survey_launches = 0, survey_segments = 0;
 };
 
 namespace {
@@ -687,6 +691,13 @@ int run_impl(aero_chan *c) {
 
   if (c->cfg.correct_dc_bias)
     hipLaunchKernelGGL(dc_kernel, dim3(1), dim3(64), 0, c->st, c->in, (long long)nb * c->B, c->avept);
+  if (c->survey) {  // the stream the main VFOs read
+    int nl = 0;
+    uint64_t ns = 0;
+    if (int rc = aero::survey_run(c->survey, c->st, c->in, (long long)nb * c->B, &nl, &ns)) return rc;
+    c->survey_launches += (uint64_t)nl;
+    c->survey_segments += ns;
+  }
   for (int sd = 0; sd < 2; sd++) {
     if (!mix[sd].empty()) {
       long long mx = 0;
@@ -764,6 +775,7 @@ int pop_vec(std::vector<T> &v, T *dst, size_t cap, size_t *n) {
 
 void destroy_impl(aero_chan *c) {
   if (c->st) (void)hipStreamSynchronize(c->st);
+  aero::survey_destroy(c->survey);
   for (void *p : c->dmem) (void)hipFree(p);
   if (c->d_jobs) (void)hipFree(c->d_jobs);
   if (c->h_jobs) (void)hipHostFree(c->h_jobs);
@@ -1137,9 +1149,39 @@ int aero_chan_stat(aero_chan *c, const char *name, uint64_t *value) {
     *value = c->vfo_inits;
   else if (!strcmp(name, "slots_free"))
     *value = c->pool.free_count();
+  else if (!strcmp(name, "survey_launches"))
+    *value = c->survey_launches;
+  else if (!strcmp(name, "survey_segments"))
+    *value = c->survey_segments;
   else
     return AERO_E_INVALID;
   return AERO_OK;
+}
+
+int aero_chan_survey_start(aero_chan *c, const aero_chan_survey_cfg *cfg) {
+  if (!c || !cfg || c->survey || (cfg->log2n != 12 && cfg->log2n != 13 && cfg->log2n != 14)) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  if (int rc = run_impl(c)) return rc;  // the reads taken so far run without it
+  if (int rc = aero::survey_create(cfg->log2n, cfg->window, (long long)c->cfg.max_blocks * c->B, &c->survey)) return rc;
+  c->dev_bytes += aero::survey_bytes(c->survey);
+  return AERO_OK;
+}
+
+int aero_chan_survey_stop(aero_chan *c) {
+  if (!c || !c->survey) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  if (int rc = run_impl(c)) return rc;  // the reads taken so far run with it
+  CHK(hipStreamSynchronize(c->st));
+  c->dev_bytes -= aero::survey_bytes(c->survey);
+  aero::survey_destroy(c->survey);
+  c->survey = nullptr;
+  return AERO_OK;
+}
+
+int aero_chan_survey_read(aero_chan *c, double *power, size_t cap, uint64_t *segments, int reset) {
+  if (!c || !c->survey) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  return aero::survey_read(c->survey, c->st, power, cap, segments, reset);
 }
 
 }  // extern "C"

@@ -17,6 +17,12 @@
  *   driver=file,path=<interleaved float32 IQ>[,loop=1][,realtime=1][,start_delay_ms=N]
  * (realtime paces reads at the INI sample rate, as a radio delivers them).
  * Any other driver fails the way SoapySDR::Device::make does.
+ *
+ * Not in the reference: the optional [General] keys survey_log2n (12, 13 or
+ * 14; absent or 0: off), survey_period (reads per report; default one
+ * second's worth), survey_threshold and survey_min_bins run the channeliser's
+ * carrier survey and log one INFO line per carrier and period:
+ *   survey: carrier <frequency> Hz bandwidth <Hz> Hz ratio <x> vfo <[vfos] id or ->
  */
 #include <execinfo.h>
 #include <signal.h>
@@ -245,6 +251,30 @@ int main(int argc, char **argv) {
   }
   int B = 0;
   aero_chan_block_len(chan, &B);
+  // Carrier survey (not in the reference, which ignores these [General]
+  // keys): survey_log2n 12..14 turns it on (absent or 0: off), a report every
+  // survey_period reads (default: one second's worth)
+  const int survey_log2n = ini.value_int("survey_log2n");
+  int survey_period = ini.value_int("survey_period");
+  if (survey_period <= 0) survey_period = Fs / B;
+  aero_survey_peak_cfg peak_cfg{8.0, 2, 2};
+  if (ini.value_float("survey_threshold") > 0) peak_cfg.threshold = ini.value_float("survey_threshold");
+  if (ini.value_int("survey_min_bins") > 0) peak_cfg.min_bins = ini.value_int("survey_min_bins");
+  std::vector<double> survey_power;
+  std::vector<aero_survey_peak> survey_found(64);
+  if (survey_log2n) {
+    const size_t n = survey_log2n >= 12 && survey_log2n <= 14 ? (size_t)1 << survey_log2n : 1;
+    std::vector<double> hann(n);
+    for (size_t i = 0; i < n; i++) hann[i] = 0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)n);
+    const aero_chan_survey_cfg sc{survey_log2n, hann.data()};
+    if (int rc = aero_chan_survey_start(chan, &sc)) {
+      AH_CRIT("[ERROR] survey_log2n=%d: %s (12, 13 or 14)", survey_log2n, aero_strerror(rc));
+      fclose(src);
+      aero_chan_destroy(chan);
+      return 1;
+    }
+    survey_power.resize(n);
+  }
   const Zmq *z = zmq_load();
   if (!z) return 1;
   void *ctx = z->ctx_new();
@@ -332,6 +362,39 @@ int main(int argc, char **argv) {
     reads++;
     tm.count("reads");
     tm.mark("publish");
+    if (!survey_power.empty() && reads % survey_period == 0) {
+      uint64_t segs = 0;
+      size_t np = 0;
+      int rc = aero_chan_survey_read(chan, survey_power.data(), survey_power.size(), &segs, 1);
+      if (!rc && segs) {
+        rc = aero_survey_peaks(survey_power.data(), survey_log2n, Fs, center, mix_offset, &peak_cfg,
+                               survey_found.data(), survey_found.size(), &np);
+        if (rc == AERO_E_FULL) {
+          survey_found.resize(np);
+          rc = aero_survey_peaks(survey_power.data(), survey_log2n, Fs, center, mix_offset, &peak_cfg,
+                                 survey_found.data(), survey_found.size(), &np);
+        }
+      }
+      if (rc) {
+        AH_CRIT("survey error: %s", aero_strerror(rc));
+        rc_exit = 1;
+        break;
+      }
+      const double binw = (double)Fs / (double)survey_power.size(), half = (double)(survey_power.size() / 2);
+      for (size_t k = 0; k < np; k++) {
+        const aero_survey_peak &p = survey_found[k];
+        // the [vfos] entry whose frequency lies inside the carrier's band
+        std::string id = "-";
+        for (size_t v = 0; v < vfos.size() && id == "-"; v++) {
+          const double off = (double)vfos[v].frequency + (double)mix_offset - (double)center;
+          if (off >= ((double)p.first_bin - half - 0.5) * binw && off <= ((double)p.last_bin - half + 0.5) * binw)
+            id = std::to_string(v);
+        }
+        AH_INF("survey: carrier %lld Hz bandwidth %.0f Hz ratio %.1f vfo %s", p.frequency, p.bandwidth_hz, p.ratio,
+               id.c_str());
+      }
+      tm.mark("survey");
+    }
   }
   tm.print("aero-publish");
   AH_DBG("reader stopped after %lld reads", reads);

@@ -156,9 +156,104 @@ int aero_chan_vfo_count(aero_chan *c, int *n);
  * always there: 124 (Hilbert) + audio taps + ceil(late taps / late) + 12 per
  * half-band stage of the VFO and of its main VFO */
 int aero_chan_vfo_settle(aero_chan *c, int v, size_t *samples);
-/* "device_bytes": device memory held; "vfo_inits": start-kernel launches;
- * "slots_free": free slots held.  Other names: AERO_E_INVALID. */
+/* "device_bytes": device memory held (a survey's buffers while one is on);
+ * "vfo_inits": start-kernel launches; "slots_free": free slots held;
+ * "survey_launches": kernel launches made for surveys since creation (0 while
+ * none was ever started); "survey_segments": segments accumulated since
+ * creation.  Other names: AERO_E_INVALID. */
 int aero_chan_stat(aero_chan *c, const char *name, uint64_t *value);
+
+/*
+ * Wideband carrier survey: an averaged power spectrum of the input, to find
+ * where [vfos] entries belong (the reference has no counterpart).
+ *
+ * Off by default; while off the channeliser launches and allocates nothing
+ * for it.  While a survey is on:
+ *
+ *  - It reads the sample stream the VFOs read: the pushed CF32 reads in
+ *    order, after the DC removal when correct_dc_bias is set and raw
+ *    otherwise.  Samples are counted from the first read that runs after
+ *    aero_chan_survey_start.
+ *  - Segment s is samples [s*N, (s+1)*N) of that stream, N = 2^log2n, log2n
+ *    12, 13 or 14.  No read length is a multiple of N, so a segment straddles
+ *    reads, batches and aero_chan_run calls; the unfinished tail (< N
+ *    samples) is carried on the device.
+ *  - Per segment, in FP64 without contraction, in this order:
+ *      x[i] = (double)re[i] * w[i], (double)im[i] * w[i]  with the caller's
+ *             window w (N doubles; NULL: no multiplication at all);
+ *      X    = the forward radix-2 transform of the decoder (JFFT,
+ *             decode/jfft.cpp:114-212, with JFFT::init's tables), bit for bit;
+ *      p[k] = X[k].re * X[k].re + X[k].im * X[k].im, natural bin order
+ *             k = 0 .. N-1 (bin k: k * sample_rate / N above the centre for
+ *             k < N/2, (k - N) * sample_rate / N for the upper half);
+ *      acc[k] = acc[k] + p[k], the sum over segments taken in stream order.
+ *    The result equals that sequential computation in every bit.
+ *  - The survey does not depend on the VFOs: entries may be opened, closed and
+ *    skipped while it runs, and no VFO's audio and no main VFO's IQ changes by
+ *    one bit when a survey starts, runs or stops.
+ *
+ * aero_chan_survey_start and _stop first run the reads that are pushed and
+ * not yet run, as aero_chan_run does (without the survey / with it): call
+ * them after aero_chan_feed / aero_chan_vfo_output have used the previous
+ * batch.  Both wait for the device (they allocate / free the buffers).
+ */
+typedef struct {
+  int log2n;             /* 12, 13 or 14 */
+  const double *window;  /* 2^log2n doubles, copied; NULL: none */
+} aero_chan_survey_cfg;
+/* AERO_E_INVALID: another log2n, or a survey is already on.  The grid starts
+ * at the next read pushed. */
+int aero_chan_survey_start(aero_chan *c, const aero_chan_survey_cfg *cfg);
+/* Drops sums, count and tail (AERO_E_INVALID: none is on).  A later start
+ * begins a fresh grid at the next read. */
+int aero_chan_survey_stop(aero_chan *c);
+/* Waits for the runs launched so far (reads pushed and not yet run are not
+ * run), then power[0 .. N) = acc and *segments = the number of segments in
+ * it; cap < N: AERO_E_INVALID.  reset != 0 then zeroes both; the carried tail
+ * and the segment grid are not reset. */
+int aero_chan_survey_read(aero_chan *c, double *power, size_t cap, uint64_t *segments, int reset);
+
+/*
+ * The carriers in a survey spectrum.  A host function: no aero_chan and no GPU
+ * is needed.  Plain FP64 loops in the order given, without contraction:
+ *
+ *  1. q[i] = power[(i + N/2) mod N], i = 0 .. N-1: ascending frequency,
+ *     f_i = (double)(i - N/2) * (double)sample_rate / (double)N.
+ *  2. floor = the lower median of q: element (N-1)/2 of the sorted copy.
+ *  3. Bin i is hot when q[i] > threshold * floor (all-zero input: none).
+ *  4. Maximal runs of hot bins; runs separated by at most merge_gap cold bins
+ *     are merged (the cold bins belong to the merged run); then runs shorter
+ *     than min_bins are dropped.  A run does not wrap around the band edge.
+ *  5. Per run [a, b], sums in ascending i: first_bin = a, last_bin = b
+ *     (indices into q); bandwidth_hz = (b - a + 1) * sample_rate / N;
+ *     ratio = (sum q[i]) / (b - a + 1) / floor (infinite over a zero floor);
+ *     offset_hz = sum((q[i] - floor) * f_i) / sum(q[i] - floor), or
+ *     (f_a + f_b) / 2 where that divisor is not positive.
+ *  6. frequency = center_frequency + llround(offset_hz) - mix_offset: the
+ *     value a [vfos] entry's `frequency` takes to be centred on the carrier.
+ *     The channeliser's mixers move the input by center_frequency -
+ *     (frequency + mix_offset) (publisher.cpp:115-222), so a carrier offset_hz
+ *     above the centre lands on 0 Hz of that entry, and an entry 1000 Hz below
+ *     `frequency` puts it at 1000 Hz of its upper-sideband audio.
+ *
+ * Peaks are written in ascending frequency.  *n is the number found; when it
+ * exceeds cap the first cap are written and AERO_E_FULL is returned.
+ * AERO_E_INVALID: log2n outside 2 .. 24, sample_rate <= 0, threshold <= 0,
+ * min_bins < 1, merge_gap < 0, or a power value that is negative or not
+ * finite.
+ */
+typedef struct {
+  double threshold;  /* hot: above threshold x the median bin */
+  int min_bins;      /* shortest run reported */
+  int merge_gap;     /* cold bins two runs may be apart and still be one */
+} aero_survey_peak_cfg;
+typedef struct {
+  double offset_hz, bandwidth_hz, ratio;
+  long long frequency;
+  int first_bin, last_bin;
+} aero_survey_peak;
+int aero_survey_peaks(const double *power, int log2n, int sample_rate, long long center_frequency, int mix_offset,
+                      const aero_survey_peak_cfg *cfg, aero_survey_peak *out, size_t cap, size_t *n);
 
 #ifdef __cplusplus
 }
