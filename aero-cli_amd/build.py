@@ -4,6 +4,7 @@
   tools/libaero_synth.so           synthetic Aero P-channel transmitter
   oracle/liboracle.so              test-only CPU restatement (checker)
   tools/liboracle_tick.so          the same plus a DCD-timer hook (checker of the burst and continuous-MSK timers)
+  tools/liboracle_ranges.so        the same with its observation hook defined (range probe; built by its tests)
 
 Usage: python aero-cli_amd/build.py [--engine] [--synth] [--oracle] [-j N]
 (no flag = everything).  Object files go to aero-cli_amd/build/.
@@ -216,6 +217,27 @@ def build_oracletick():
               '-Wno-subobject-linkage', '-Wl,-Bsymbolic', '-shared', '-o', ORACLETICK_SO, src,
               os.path.join(ORACLE_DIR, 'pub_oracle.cpp'), '-lm'])
     return ORACLETICK_SO
+
+
+ORACLERANGES_SO = os.path.join(ROOT, 'tools', 'liboracle_ranges.so')
+
+
+def build_oracleranges():
+    """Test-only: the oracle as it stands with its observation hook defined
+    (tools/oracle_ranges.cpp): which libm calls and divisions of the continuous
+    demodulators leave the kernels' fast ranges on a given stream
+    (tests/cont_inputs.py).  Built by the tests that use it, not by build_all();
+    build_oracletick()'s flags."""
+    src = os.path.join(ROOT, 'tools', 'oracle_ranges.cpp')
+    deps = [src] + [os.path.join(ORACLE_DIR, f) for f in ('aero_oracle.cpp', 'pub_oracle.cpp', 'aero_oracle.h')]
+    deps += [os.path.join(CSRC, h) for h in ('aero_math.h', 'aero_glibc_tables.h')]  # the ranges are aero_math.h's
+    if _stale(ORACLERANGES_SO, deps):
+        tmp = '%s.%d.tmp' % (ORACLERANGES_SO, os.getpid())  # renamed into place: never loaded half written
+        _run(['g++', '-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Wextra',
+              '-Wno-subobject-linkage', '-Wl,-Bsymbolic', '-shared', '-o', tmp, src,
+              os.path.join(ORACLE_DIR, 'pub_oracle.cpp'), '-lm'])
+        os.replace(tmp, ORACLERANGES_SO)
+    return ORACLERANGES_SO
 
 
 HOST = os.path.join(HERE, 'host')

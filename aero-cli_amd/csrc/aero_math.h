@@ -104,10 +104,13 @@ AERO_HD double div_c(double a, double c) {
 /* div_c behind a wave-uniform test of its contract (every lane's numerator
  * zero or at least 2^-900 in magnitude), the IEEE division otherwise: for
  * numerators whose range is not argued, e.g. 360 x a phase pointer */
+AERO_HD bool in_div_cw(double a) {
+  const double m = __builtin_fabs(a);
+  return m == 0.0 || m >= 0x1p-900;
+}
 AERO_HD double div_cw(double a, double c) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  const double m = __builtin_fabs(a);
-  if (__builtin_expect(__all(m == 0.0 || m >= 0x1p-900), 1)) return div_c(a, c);
+  if (__builtin_expect(__all(in_div_cw(a)), 1)) return div_c(a, c);
 #endif
   return a / c;
 }
@@ -220,12 +223,18 @@ AERO_HD double aero_hypot_nr(double x, double y) {
 }
 
 /* aero_hypot with aero_hypot_nr when every active lane of the wave is in its
- * range (one uniform branch), the general code otherwise */
+ * range (one uniform branch), the general code otherwise.  The in_* tests of
+ * one lane's arguments are host code too: tools/oracle_ranges.cpp counts the
+ * oracle's calls that fail them.  Where a fast form uses a high word or an
+ * |x| again, the device hands the test that value (in_tanh_hi, in_sincos_hi,
+ * in_atan2_abs): a test that computes its own compiles to other code. */
+AERO_HD bool in_hypot_w(double x, double y) {
+  const double a = __builtin_fabs(x), b = __builtin_fabs(y);
+  return a <= 0x1p200 && b <= 0x1p200 && (a >= 0x1p-200 || b >= 0x1p-200);
+}
 AERO_HD double aero_hypot_w(double x, double y) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  const double a = __builtin_fabs(x), b = __builtin_fabs(y);
-  const bool nr = a <= 0x1p200 && b <= 0x1p200 && (a >= 0x1p-200 || b >= 0x1p-200);
-  if (__builtin_expect(__all(nr), 1)) return aero_hypot_nr(x, y);
+  if (__builtin_expect(__all(in_hypot_w(x, y)), 1)) return aero_hypot_nr(x, y);
 #endif
   return aero_hypot(x, y);
 }
@@ -405,11 +414,12 @@ AERO_HD double g_expm1_tanh_bf(double x) {
  * 1 - 2 / (t + 2) with t = expm1(2|x|) for |x| >= 1, -t / (t + 2) with
  * t = expm1(-2|x|) below; both quotients are in div_r's contract (t + 2 in
  * (1.13, 2) or >= 8.3, the numerator 2 or |t| >= 2^-54). */
+AERO_HD bool in_tanh_hi(int32_t ix) { return ix < 0x40360000 && ix >= 0x3c800000; }  // ix: |x|'s high word
+AERO_HD bool in_tanh_bf(double x) { return in_tanh_hi((int32_t)hiw(x) & 0x7fffffff); }
 AERO_HD double aero_tanh_bf(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const int32_t jx = (int32_t)hiw(x), ix = jx & 0x7fffffff;
-  const bool ok = ix < 0x40360000 && ix >= 0x3c800000;
-  if (!__builtin_expect(__all(ok), 1)) return aero_tanh_cold(x);
+  if (!__builtin_expect(__all(in_tanh_hi(ix)), 1)) return aero_tanh_cold(x);
   const bool big = ix >= 0x3ff00000;
   const double ax = __builtin_fabs(x);
   const double t = g_expm1_tanh_bf(big ? 2.0 * ax : -2.0 * ax);
@@ -606,10 +616,12 @@ AERO_HD void aero_sincos(double x, double &so, double &co) { aero_sincos_t(x, so
  * do_sin is the Taylor form below 0.126 and the table form above: all four
  * are evaluated and selected, the two table forms on the one row of
  * u = BIG + |x|. */
+AERO_HD bool in_sincos_hi(uint32_t k) { return k < 0x3feb6000u; }  // k: |x|'s high word
+AERO_HD bool in_sincos_bf(double x) { return in_sincos_hi(hiw(x) & 0x7fffffffu); }
 AERO_HD void aero_sincos_bf(double x, double &so, double &co, const double *sct) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const uint32_t k = hiw(x) & 0x7fffffffu;
-  if (!__builtin_expect(__all(k < 0x3feb6000u), 1)) {
+  if (!__builtin_expect(__all(in_sincos_hi(k)), 1)) {
     aero_sincos_cold(x, so, co, sct);
     return;
   }
@@ -816,13 +828,20 @@ AERO_HD double aero_atan2(double y, double x) { return aero_atan2_t(y, x, aero_g
  *     fma(s v, P, K1) (table), where multiplying by s = +-1 is exact and
  *     x + (-y) is x - y bit for bit;
  *   - the table forms share v = (u - c0) + du and P = fma(v, p3, c2). */
+AERO_HD int32_t atan2_de(double y, double x) {  // y's exponent field less x's, at bit 20
+  return (int32_t)((hiw(y) & 0x7ff00000u) - (hiw(x) & 0x7ff00000u));
+}
+AERO_HD bool in_atan2_abs(double ax, double ay, int32_t de) {  // |x|, |y|, atan2_de(y, x)
+  return ax >= 0x1p-500 && ax <= 0x1p500 && ay >= 0x1p-500 && ay <= 0x1p500 && de < 59768832 && de > -59768832;
+}
+AERO_HD bool in_atan2_bf(double y, double x) {
+  return in_atan2_abs(__builtin_fabs(x), __builtin_fabs(y), atan2_de(y, x));
+}
 AERO_HD double aero_atan2_bf(double y, double x, const double (*cij)[7]) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
-  const int32_t de = (int32_t)((hiw(y) & 0x7ff00000u) - (hiw(x) & 0x7ff00000u));
-  const bool ok = ax >= 0x1p-500 && ax <= 0x1p500 && ay >= 0x1p-500 && ay <= 0x1p500 && de < 59768832 &&
-                  de > -59768832;
-  if (!__builtin_expect(__all(ok), 1)) return aero_atan2_cold(y, x, cij);
+  const int32_t de = atan2_de(y, x);
+  if (!__builtin_expect(__all(in_atan2_abs(ax, ay, de)), 1)) return aero_atan2_cold(y, x, cij);
   const bool gt = ax > ay;  // u = ay / ax, else u = ax / ay
   const double a = gt ? ay : ax, b = gt ? ax : ay;
   const double r = rcp_div(b);

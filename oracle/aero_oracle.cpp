@@ -64,6 +64,29 @@ namespace {
 typedef std::complex<double> cpx;
 const int WTSIZE = 19999;
 
+// Observation points of the continuous demodulators' per-sample loops: the
+// arguments of their libm calls and the numerators of the divisions that the
+// engine's kernels shorten.  tools/oracle_ranges.cpp defines ORACLE_OBS before
+// it includes this file and counts the calls outside the kernels' fast ranges;
+// here the hook expands to nothing, and no output depends on it.
+enum {
+  OBS_HYPOT,      // std::abs(sig2) (OQPSK, C), std::abs(pt_msk) (MSK): (re, im)
+  OBS_ATAN2,      // olm::arg(st_out): (im, re)
+  OBS_TANH,       // the two carrier-loop tanh calls: (x, 0)
+  OBS_TANH_ST,    // MSK: tanh(st_angle_error)
+  OBS_SINCOS,     // cos / sin(marg.Val)
+  OBS_MSE_HYPOT,  // MSEcalc's std::abs(pt_qpsk)
+  OBS_DIV_AGC,    // AGCMASum / AGCMASz
+  OBS_DIV_TW,     // t_WTptr / WTstep (FractionOfSampleItPassesBy): (numerator, divisor)
+  OBS_DIV_NUDGE,  // -st_angle_error * 0.01 / 360.0 (OQPSK, C)
+  OBS_DIV_M2PTR,  // 360.0 * WTptr / WTSIZE (IncresePhaseDeg)
+  OBS_DIV_MSSUM,  // MSEcalc's msema sum / its length
+  OBS_SITES
+};
+#ifndef ORACLE_OBS
+#define ORACLE_OBS(site, a, b) ((void)0)
+#endif
+
 // the libm calls of the per-sample loops, as the reference makes them
 namespace olm {
 double sin(double x) { return ::sin(x); }
@@ -139,6 +162,7 @@ struct WaveTable {
     WTptr = (phase_deg / 360.0) * ((double)WTSIZE);
   }
   void IncresePhaseDeg(double phase_deg) {
+    ORACLE_OBS(OBS_DIV_M2PTR, 360.0 * WTptr, 0.0);
     phase_deg += (360.0 * WTptr / ((double)WTSIZE));
     SetPhaseDeg(phase_deg);
   }
@@ -156,6 +180,7 @@ struct WaveTable {
     if (t_last_WTptr < 0.0) t_last_WTptr += WTSIZE;
     if (t_WTptr < 0.0) t_WTptr += WTSIZE;
     if ((t_last_WTptr > 3.0 * WTSIZE / 4.0) && (t_WTptr < 1.0 * WTSIZE / 4.0)) {
+      ORACLE_OBS(OBS_DIV_TW, t_WTptr, WTstep);
       FractionOfSampleItPassesBy = t_WTptr / WTstep;
       return true;
     }
@@ -253,6 +278,7 @@ struct MSEcalc {
   double Update(cpx pt_qpsk) {
     double tda, tdb;
     cpx tcpx;
+    ORACLE_OBS(OBS_MSE_HYPOT, pt_qpsk.real(), pt_qpsk.imag());
     pointmean.Update(std::abs(pt_qpsk));
     double mu = pointmean.Val;
     if (mu < 0.000001) mu = 0.000001;
@@ -260,6 +286,7 @@ struct MSEcalc {
     tda = (fabs(tcpx.real()) - 1.0);
     tdb = (fabs(tcpx.imag()) - 1.0);
     mse = msema.Update((tda * tda) + (tdb * tdb));
+    ORACLE_OBS(OBS_DIV_MSSUM, msema.MASum, 0.0);
     return mse;
   }
 };
@@ -2329,6 +2356,8 @@ struct Oqpsk {
       }
       double dabval = std::sqrt(sig2.real() * sig2.real() + sig2.imag() * sig2.imag());
       sig2 *= agc.Update(dabval);
+      ORACLE_OBS(OBS_DIV_AGC, agc.AGCMASum, 0.0);
+      ORACLE_OBS(OBS_HYPOT, sig2.real(), sig2.imag());
       double abval = std::abs(sig2);
       if (abval > 2.84) sig2 = (2.84 / abval) * sig2;
       double st_diff = delays.update(abval * abval) - (abval * abval);
@@ -2338,7 +2367,9 @@ struct Oqpsk {
       st_eta = st_iir_resonator.update(st_eta);
       cpx st_m1 = cpx(st_eta, -delayt8.update(st_eta));
       cpx st_out = st_osc.WTCISValue() * st_m1;
+      ORACLE_OBS(OBS_ATAN2, st_out.imag(), st_out.real());
       double st_angle_error = olm::arg(st_out);
+      ORACLE_OBS(OBS_DIV_NUDGE, -st_angle_error * 0.01, 0.0);
       st_osc.IncreseFreqHz(-st_angle_error * 0.00000001);
       st_osc.AdvanceFractionOfWave(-st_angle_error * 0.01 / 360.0);
       if (st_osc.GetFreqHz() < (st_osc_ref.GetFreqHz() - 0.1))
@@ -2359,6 +2390,8 @@ struct Oqpsk {
           pt_d = pt;
         else {
           cpx pt_qpsk = cpx(pt.real(), pt_d.imag());
+          ORACLE_OBS(OBS_TANH, pt.imag(), 0.0);
+          ORACLE_OBS(OBS_TANH, pt_d.real(), 0.0);
           double ct_xt = tanh(pt.imag()) * pt.real();
           double ct_xt_d = tanh(pt_d.real()) * pt_d.imag();
           double ct_ec = ct_xt_d - ct_xt;
@@ -2376,6 +2409,7 @@ struct Oqpsk {
           }
           marg.UpdateSigned(ct_ec);
           dt.update(pt_qpsk);
+          ORACLE_OBS(OBS_SINCOS, marg.Val, 0.0);
           pt_qpsk *= cpx(olm::cos(marg.Val), olm::sin(marg.Val));
           if (trace_pt) {
             pts.push_back(pt_qpsk.real());
@@ -2598,16 +2632,22 @@ struct Msk {
         pt_d = tmp;
       }
       cpx pt_msk = cpx(sig2.real(), pt_d.imag());
+      ORACLE_OBS(OBS_DIV_AGC, agc.AGCMASum, 0.0);
+      ORACLE_OBS(OBS_HYPOT, pt_msk.real(), pt_msk.imag());
       double st_eta = st_iir_resonator.update(std::abs(pt_msk));
       cpx st_m1 = cpx(st_eta, -delayt8.update(st_eta));
       cpx st_out = st_osc.WTCISValue() * st_m1;
+      ORACLE_OBS(OBS_ATAN2, st_out.imag(), st_out.real());
       double st_angle_error = olm::arg(st_out);
+      ORACLE_OBS(OBS_TANH_ST, st_angle_error, 0.0);
       double weighting = fabs(tanh(st_angle_error));
       if (!dcd)
         st_osc.AdvanceFractionOfWave(-(1.0 - weighting) * st_angle_error * (0.05 / 360.0));
       else
         st_osc.AdvanceFractionOfWave(-(1.0 - weighting) * st_angle_error * (0.003 / 360.0));
       if (st_osc.IfHavePassedPoint(ee)) {
+        ORACLE_OBS(OBS_TANH, sig2.imag(), 0.0);
+        ORACLE_OBS(OBS_TANH, pt_d.real(), 0.0);
         double ct_xt = tanh(sig2.imag()) * sig2.real();
         double ct_xt_d = tanh(pt_d.real()) * pt_d.imag();
         double ct_ec = ct_xt_d - ct_xt;
@@ -2621,6 +2661,7 @@ struct Msk {
         mixer2.IncreseFreqHz(carrier_aggression * 0.01 * ct_ec);
         marg.UpdateSigned(ct_ec / 2.0);
         dt.update(pt_msk);
+        ORACLE_OBS(OBS_SINCOS, marg.Val, 0.0);
         pt_msk *= cpx(olm::cos(marg.Val), olm::sin(marg.Val));
         if (trace_pt) {
           pts.push_back(pt_msk.real());

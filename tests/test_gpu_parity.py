@@ -1,13 +1,13 @@
 """GPU parity: the HIP engine vs the CPU oracle on the same synthetic VFO
 streams.  Integer outputs (soft bits, coarse-hop decisions, Viterbi blocks,
-CRC-checked frames, ACARS items) must be bit-exact; the rotated pt_qpsk
-soft-metric floats within 1e-5 (BASELINE.json north_star)."""
+CRC-checked frames, ACARS items) must be bit-exact, and so must the rotated
+pt_qpsk soft-metric floats, by f64 bit pattern (BASELINE.json's north star
+allows them 1e-5; they are bit-equal on every class of
+tests/test_gpu_cont_inputs.py)."""
 import numpy as np
 import pytest
 
 import aero_testlib as tl
-
-PT_TOL = 1e-5
 
 CASES = [
     # seed, carrier Hz, Eb/N0 dB, seconds, message size (samples)
@@ -52,7 +52,7 @@ def test_engine_matches_oracle(engine_lib, oqpsk_kernel):
         assert np.array_equal(h_e, h_o), 'case %d hop records differ' % k
         p_o, p_e = o.pt(), eng.pt(ch)
         assert p_o.shape == p_e.shape
-        assert np.max(np.abs(p_o - p_e)) <= PT_TOL
+        assert np.array_equal(p_e.view(np.int64), p_o.view(np.int64)), 'case %d pt values differ' % k
         assert np.array_equal(eng.blocks(ch), o.blocks()), 'case %d Viterbi blocks differ' % k
         assert np.array_equal(eng.frames(ch), o.frames()), 'case %d frames differ' % k
         items_o = o.item_lines('A')
