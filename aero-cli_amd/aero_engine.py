@@ -33,6 +33,7 @@ F_TRACE_FRAMES = 0x20
 F_DCD_TICK = 0x40  # AeroL's 1 s DCD timer on the sample clock (continuous OQPSK)
 F_DCD_TICK_BURST = 0x80  # the timer on burst channels: a tick at the end of the message that completes a second
 F_DCD_TICK_CONT = 0x100  # the timer on continuous MSK and C channels, on the sample clock (their DCD can fall)
+F_EBNO = 0x200  # continuous OQPSK / C: the reference's Eb/N0 estimate (channel_quality, pop_ebno)
 F_TRACE_ALL = F_TRACE_PT | F_TRACE_BLOCKS | F_TRACE_SOFT | F_TRACE_HOPS | F_TRACE_FRAMES
 
 MATH_FN = {'hypot': 0, 'atan2': 1, 'tanh': 2, 'sin': 3, 'cos': 4, 'log10': 5, 'sqrt': 6, 'fmod360': 7,
@@ -105,6 +106,12 @@ class ChannelEvents(ctypes.Structure):
     _fields_ = [('dcd_edges', ctypes.c_int64), ('hunter_steps', ctypes.c_int64), ('hunter_fc', ctypes.c_double * 8)]
 
 
+class ChannelQuality(ctypes.Structure):
+    _fields_ = [('samples', ctypes.c_int64), ('ebno_db', ctypes.c_double), ('mse', ctypes.c_double),
+                ('mixer_hz', ctypes.c_double), ('center_hz', ctypes.c_double), ('signal', ctypes.c_int32),
+                ('ebno_valid', ctypes.c_int32)]
+
+
 # every entry point declared in include/aero_engine.h and include/aero_chan.h (tests/test_abi.py checks the header)
 _SIGS = {
     'aero_engine_create': (ctypes.c_int, [ctypes.POINTER(EngineCfg), ctypes.POINTER(ctypes.c_void_p)]),
@@ -156,6 +163,9 @@ _SIGS = {
     'aero_channel_stat': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p,
                                          ctypes.POINTER(ctypes.c_int64)]),
     'aero_channel_get_events': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ChannelEvents)]),
+    'aero_channel_get_quality': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ChannelQuality)]),
+    'aero_pop_ebno': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_size_t)]),
     'aero_sync': (ctypes.c_int, [ctypes.c_void_p]),
     'aero_device_math': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_size_t]),
@@ -521,8 +531,9 @@ class Engine:
 
     def stat(self, name):
         """aero_stat counter: 'viterbi_jobs', 'frames', 'su_crc_ok' (and burst 'rt_*'), or the
-        continuous groups' 'device_bytes' / 'groups', 'slot_resets' (reset-kernel launches) or
-        'slot_copies' (pack / unpack launches of export_channels / import_channels)."""
+        continuous groups' 'device_bytes' / 'groups', 'slot_resets' (reset-kernel launches),
+        'slot_copies' (pack / unpack launches of export_channels / import_channels) or
+        'ebno_launches' (launches of the Eb/N0 kernel, F_EBNO)."""
         v = ctypes.c_uint64()
         _check(self.lib.aero_stat(self.h, name.encode(), ctypes.byref(v)), 'aero_stat')
         return int(v.value)
@@ -541,6 +552,18 @@ class Engine:
         n = int(ev.hunter_steps)
         fcs = [ev.hunter_fc[(k - 1) & 7] for k in range(max(1, n - 7), n + 1)]
         return int(ev.dcd_edges), n, fcs
+
+    def channel_quality(self, ch):
+        """aero_channel_get_quality: dict of samples, ebno_db, mse, mixer_hz, center_hz, signal,
+        ebno_valid (ebno_db only with F_EBNO on a continuous OQPSK or C channel)."""
+        q = ChannelQuality()
+        _check(self.lib.aero_channel_get_quality(self.h, ch, ctypes.byref(q)), 'aero_channel_get_quality')
+        return dict(samples=int(q.samples), ebno_db=q.ebno_db, mse=q.mse, mixer_hz=q.mixer_hz,
+                    center_hz=q.center_hz, signal=int(q.signal), ebno_valid=int(q.ebno_valid))
+
+    def ebno(self, ch):
+        """aero_pop_ebno: [n, 2] (sample index, EbNo) per hop boundary reached (F_EBNO | F_TRACE_HOPS)."""
+        return self._pop(self.lib.aero_pop_ebno, ch, np.float64, 2)
 
     def samples_processed(self):
         return int(self.lib.aero_samples_processed(self.h))

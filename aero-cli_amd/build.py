@@ -4,6 +4,7 @@
   tools/libaero_synth.so           synthetic Aero P-channel transmitter
   oracle/liboracle.so              test-only CPU restatement (checker)
   tools/liboracle_tick.so          the same plus a DCD-timer hook (checker of the burst and continuous-MSK timers)
+  tools/liboracle_ebno.so          the same plus the reference's Eb/N0 estimator restated (checker of AERO_F_EBNO)
   tools/liboracle_ranges.so        the same with its observation hook defined (range probe; built by its tests)
 
 Usage: python aero-cli_amd/build.py [--engine] [--synth] [--oracle] [-j N]
@@ -33,7 +34,7 @@ CXX_FLAGS = ['-O2', '-std=c++17', '-fPIC', '-Wall'] + FP
 
 HIP_SRCS = ['demod_oqpsk.hip', 'demod_msk.hip', 'coarse.hip', 'aerol.hip', 'engine.hip', 'chan.hip', 'burst.hip', 'burst_msk.hip',
             'burst_engine.hip', 'cchan.hip', 'slot_reset.hip', 'slot_copy.hip', 'viterbi_probe.hip',
-            'fft_probe.hip', 'survey.hip']
+            'fft_probe.hip', 'survey.hip', 'ebno.hip']
 CXX_SRCS = ['tables_host.cpp', 'acars_host.cpp', 'chan_blob.cpp', 'survey_host.cpp']
 # Per-file codegen: the burst demodulators' loops hold their state in
 # registers; LLVM's machine LICM hoists every FP64 constant of the inlined
@@ -170,7 +171,8 @@ HOSTCHECK_SRCS = [os.path.join(ROOT, 'tools', 'hostcheck.cpp'), os.path.join(CSR
 
 def build_hostcheck(out=HOSTCHECK_SO, extra=()):
     """Test-only CPU harness over the engine's host C++ (acars_host, tables_host)."""
-    deps = HOSTCHECK_SRCS + [os.path.join(CSRC, h) for h in ('acars_host.h', 'chan_blob.h', 'dcd_host.h', 'tables_host.h')]
+    deps = HOSTCHECK_SRCS + [os.path.join(CSRC, h) for h in ('acars_host.h', 'chan_blob.h', 'dcd_host.h', 'tables_host.h',
+                                                              'ebno.h', 'aero_math.h', 'aero_glibc_tables.h')]
     if _stale(out, deps):
         _run(['g++'] + CXX_FLAGS + list(extra) + ['-shared', '-o', out] + HOSTCHECK_SRCS + ['-lm'])
     return out
@@ -217,6 +219,24 @@ def build_oracletick():
               '-Wno-subobject-linkage', '-Wl,-Bsymbolic', '-shared', '-o', ORACLETICK_SO, src,
               os.path.join(ORACLE_DIR, 'pub_oracle.cpp'), '-lm'])
     return ORACLETICK_SO
+
+
+ORACLEEBNO_SO = os.path.join(ROOT, 'tools', 'liboracle_ebno.so')
+
+
+def build_oracleebno():
+    """Test-only: the oracle as it stands plus a plain restatement of the reference's Eb/N0
+    estimator fed from the oracle's AGC buffer (tools/oracle_ebno.cpp; tests/ebno_lib.py), the
+    checker of AERO_F_EBNO.  build_oracletick()'s flags."""
+    src = os.path.join(ROOT, 'tools', 'oracle_ebno.cpp')
+    deps = [src] + [os.path.join(ORACLE_DIR, f) for f in ('aero_oracle.cpp', 'pub_oracle.cpp', 'aero_oracle.h')]
+    if _stale(ORACLEEBNO_SO, deps):
+        tmp = '%s.%d.tmp' % (ORACLEEBNO_SO, os.getpid())  # renamed into place: never loaded half written
+        _run(['g++', '-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Wextra',
+              '-Wno-subobject-linkage', '-Wl,-Bsymbolic', '-shared', '-o', tmp, src,
+              os.path.join(ORACLE_DIR, 'pub_oracle.cpp'), '-lm'])
+        os.replace(tmp, ORACLEEBNO_SO)
+    return ORACLEEBNO_SO
 
 
 ORACLERANGES_SO = os.path.join(ROOT, 'tools', 'liboracle_ranges.so')
@@ -333,6 +353,7 @@ def build_asan(jobs=4):
 def build_all(jobs=4):
     build_oracle()
     build_oracletick()
+    build_oracleebno()
     build_synth()
     build_mathhost()
     build_fftsim()

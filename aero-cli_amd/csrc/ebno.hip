@@ -1,0 +1,96 @@
+// ebno.hip — per-channel Eb/N0 (AERO_F_EBNO): the reference's
+// OQPSKEbNoMeasure over the AGC ring the demod kernels already keep (ebno.h).
+//
+// Launched after the demod launch of an OQPSK or C group whose engine has the
+// flag.  One lane per channel: the lane takes the samples the demod has
+// consumed since the estimator's last launch, [done, LS_NSAMP), from the
+// time-major ring S.agc[AGC_LEN][C] (a wave reads contiguous doubles per row)
+// and leaves the two sums, the smoothed EbNo and the new done-count.  A demod
+// launch covers at most the PCM ring (engine.hip PCM_CAP = 65536 samples), so
+// the entries of its samples and the entries EBNO_LEN behind them are still
+// in the ring (engine.hip asserts PCM_CAP <= AGC_LEN - EBNO_LEN; a lane that
+// finds a longer span leaves its state alone).
+//
+// Only the sums and the 0.8 / 0.2 recurrence are serial.  The loop takes four
+// samples a turn: their sums one after the other, then the four tebno values
+// (two divisions by a constant, one IEEE division and a log10 each), which
+// depend on nothing but their own sums and overlap in the pipeline, then the
+// four recurrence steps.  The result is the serial one bit for bit: the same
+// operations on the same operands.
+#include <hip/hip_runtime.h>
+
+#include "ebno.h"
+#include "engine_common.h"
+
+namespace aero {
+
+namespace {
+
+constexpr int EBNO_UNROLL = 4;
+constexpr int EBNO_WG = 64;  // one wave a workgroup: 64 channels, spread over the CUs
+
+__global__ __launch_bounds__(EBNO_WG) void ebno_kernel(EbnoDev E, const double *__restrict__ agc,
+                                                       const int *__restrict__ agc_ptr,
+                                                       const long long *__restrict__ nsamp_row, int C, int nch,
+                                                       int agc_len, double fb, int hop) {
+  const int c = blockIdx.x * EBNO_WG + threadIdx.x;
+  if (c >= nch) return;
+  const long long nsamp = nsamp_row[c], done = E.done[c];
+  long long left = nsamp - done;
+  // nothing new; or a span the ring no longer holds (no demod launch gives one)
+  if (left <= 0 || left > (long long)(agc_len - EBNO_LEN)) return;
+  double s1 = E.acc[c], s2 = E.acc[(size_t)C + c], eb = E.acc[(size_t)2 * C + c];
+  int row = (int)((agc_ptr[c] - left % agc_len + agc_len) % agc_len);  // in [0, agc_len)
+  auto older = [agc_len](int r) { return r >= EBNO_LEN ? r - EBNO_LEN : r - EBNO_LEN + agc_len; };
+  auto next = [agc_len](int r) { return r + 1 == agc_len ? 0 : r + 1; };
+  for (; left >= EBNO_UNROLL; left -= EBNO_UNROLL) {
+    double a[EBNO_UNROLL], o[EBNO_UNROLL], q1[EBNO_UNROLL], q2[EBNO_UNROLL], t[EBNO_UNROLL];
+#pragma unroll
+    for (int k = 0; k < EBNO_UNROLL; ++k) {
+      a[k] = agc[(size_t)row * C + c];
+      o[k] = agc[(size_t)older(row) * C + c];
+      row = next(row);
+    }
+#pragma unroll
+    for (int k = 0; k < EBNO_UNROLL; ++k) {
+      ebno_sums(s1, s2, a[k], o[k]);
+      q1[k] = s1;
+      q2[k] = s2;
+    }
+#pragma unroll
+    for (int k = 0; k < EBNO_UNROLL; ++k) t[k] = ebno_tebno(q1[k], q2[k], fb);
+#pragma unroll
+    for (int k = 0; k < EBNO_UNROLL; ++k) eb = ebno_smooth(eb, t[k]);
+  }
+  for (; left > 0; --left) {
+    eb = ebno_step(s1, s2, eb, agc[(size_t)row * C + c], agc[(size_t)older(row) * C + c], fb);
+    row = next(row);
+  }
+  E.acc[c] = s1;
+  E.acc[(size_t)C + c] = s2;
+  E.acc[(size_t)2 * C + c] = eb;
+  E.done[c] = nsamp;
+  // the channel stands on a hop boundary: the value the reference emits with
+  // that hop (FreqOffsetEstimateSlot runs before the hop sample's own Update,
+  // decode/oqpskdemodulator.cpp:351-402, :614)
+  if (E.tr && (nsamp + 1) % hop == 0) {
+    const int k = E.tr_n[c];
+    if (k < E.tr_cap) {
+      double *r = E.tr + ((size_t)c * E.tr_cap + k) * 2;
+      r[0] = (double)nsamp;
+      r[1] = eb;
+    }
+    E.tr_n[c] = k + 1;
+  }
+}
+
+}  // namespace
+
+void launch_ebno(hipStream_t st, const EbnoDev &E, const DevState &S, int nch, double fb) {
+  if (nch <= 0) return;
+  hipLaunchKernelGGL(ebno_kernel, dim3((unsigned)((nch + EBNO_WG - 1) / EBNO_WG)), dim3(EBNO_WG), 0, st, E,
+                     (const double *)S.agc, (const int *)(S.is + (size_t)IS_AGC_PTR * S.C),
+                     (const long long *)(S.ls + (size_t)LS_NSAMP * S.C), S.C, nch, S.g.agc_len, fb, S.g.hop);
+}
+
+}  // namespace aero

@@ -40,6 +40,7 @@
 #include "aero_math.h"
 #include "chan_blob.h"
 #include "dcd_host.h"
+#include "ebno.h"
 #include "engine_common.h"
 #include "fft_layout.h"
 #include "host_pool.h"
@@ -68,6 +69,8 @@ void launch_prefilter_c(hipStream_t, const DevState &, const DevTables &, const 
 void launch_demod_c(hipStream_t, const DevState &, const DevTables &, int, bool);
 void upload_c_constants(const DelayDesc *);
 int c_prejob_bytes();
+// ebno.hip
+void launch_ebno(hipStream_t, const EbnoDev &, const DevState &, int, double);
 // slot_reset.hip
 void launch_reset_slots(hipStream_t, void *, const ResetSeg *, int, const int *, const int *, int, const ResetInit *,
                         unsigned long long);
@@ -81,6 +84,9 @@ constexpr int GENERIC_GROUP_CAP = 256;  // channels per generic-rate MSK group
 constexpr long long PCM_CAP = 65536;  // per-channel PCM ring: a second of 48 kHz audio per run without an early pass
 constexpr int PT_CAP = 4096;
 constexpr int HOP_CAP = 64;
+// AERO_F_EBNO: after a demod launch the AGC ring still holds the launch's samples and the
+// entries EBNO_LEN behind them, which the estimator's moving averages drop (ebno.h)
+static_assert(PCM_CAP <= AGC_LEN - EBNO_LEN, "a demod launch must not outrun the Eb/N0 estimator's window in the AGC ring");
 
 #define HIPCHK(x)                                   \
   do {                                              \
@@ -234,6 +240,12 @@ struct Group {
   std::vector<std::vector<uint8_t>> infofield;  // 600/1200: the frame being assembled from its blocks
   std::vector<std::vector<int16_t>> soft_hold;
   std::vector<std::vector<double>> hop_hold, pt_hold;
+  // AERO_F_EBNO on an OQPSK or C group (ebno.hip): the estimator's device
+  // arrays (null without the flag), its launches (aero_stat "ebno_launches"),
+  // and with AERO_F_TRACE_HOPS the (sample index, EbNo) records collected
+  EbnoDev EB{};
+  uint64_t ebno_launches = 0;
+  std::vector<std::vector<double>> ebno_hold;
   std::vector<std::vector<uint8_t>> blk_hold, frame_hold;
   std::vector<long long> soft_seen;
   // samples the channel demodulated before it moved into this group (an MSK
@@ -387,7 +399,7 @@ namespace {
 // notes in `rec` how a channel's part of it is addressed: the per-channel
 // entries are the reset plan of a slot (group_reset_plan, aero_x_reset_plan).
 size_t layout(DevState &S, DevTables &T, int mode, const ModeGeom &g, int C, int flags, char *base,
-              LayoutRec *rec = nullptr) {
+              LayoutRec *rec = nullptr, EbnoDev *EB = nullptr) {
   const bool msk = mode != MODE_OQPSK && mode != MODE_C8400;
   char *p = base;
   if (rec) rec->C = C;
@@ -475,6 +487,22 @@ size_t layout(DevState &S, DevTables &T, int mode, const ModeGeom &g, int C, int
   shared(T.twgi, g.nfft);
   shared(T.scr, 5000);
   shared(T.taps, MAX_TAPS);
+  // AERO_F_EBNO (OQPSK and the C channel, whose AGC ring spans the estimator's
+  // window): the two sums and the smoothed EbNo, the done-count, and with
+  // AERO_F_TRACE_HOPS the per-hop records.  Per-channel arrays like the rest:
+  // the reset plan, the pack / unpack kernels and the fingerprint cover them.
+  // Without the flag nothing is carved and the pool is what it was.
+  EbnoDev eb{};
+  if (!msk && (flags & AERO_F_EBNO)) {
+    col(eb.acc, 3);
+    col(eb.done, 1);
+    if (flags & AERO_F_TRACE_HOPS) {
+      eb.tr_cap = HOP_CAP;
+      row(eb.tr, (size_t)HOP_CAP * 2);
+      row(eb.tr_n, 1);
+    }
+  }
+  if (EB) *EB = eb;
   return (size_t)(p - base);
 }
 
@@ -859,6 +887,24 @@ int collect_traces(Group *e) {
     }
     HIPCHK(hipMemset(e->S.hop_n, 0, sizeof(int) * nch));
   }
+  if (e->EB.tr) {
+    HIPCHK(hipMemcpy(hn.data(), e->EB.tr_n, sizeof(int) * nch, hipMemcpyDeviceToHost));
+    bool anyeb = false;
+    for (int c = 0; c < nch; c++) anyeb |= hn[c] > 0;
+    if (anyeb) {
+      const size_t rec = (size_t)HOP_CAP * 2;
+      std::vector<double> h(rec * (rows ? 1 : nch));
+      if (!rows) HIPCHK(hipMemcpy(h.data(), e->EB.tr, h.size() * 8, hipMemcpyDeviceToHost));
+      for (int c : sel) {
+        const int n = std::min(hn[c], HOP_CAP);
+        if (n <= 0) continue;
+        const double *src = h.data() + (rows ? 0 : (size_t)c * rec);
+        if (rows) HIPCHK(hipMemcpy(h.data(), e->EB.tr + (size_t)c * rec, (size_t)n * 2 * 8, hipMemcpyDeviceToHost));
+        e->ebno_hold[c].insert(e->ebno_hold[c].end(), src, src + (size_t)n * 2);
+      }
+      HIPCHK(hipMemset(e->EB.tr_n, 0, sizeof(int) * nch));
+    }
+  }
   if (e->flags & AERO_F_TRACE_PT) {
     std::vector<long long> pn(nch);
     HIPCHK(hipMemcpy(pn.data(), e->S.ls + (size_t)LS_PT_N * C, 8 * nch, hipMemcpyDeviceToHost));
@@ -1125,6 +1171,14 @@ int run_pass(Group *e, int flush, bool *more) {
     else
       launch_demod_msk(e->st, e->mode, e->S, e->T, e->nch, flush, e->nch <= e->wide_max);
     ev_end(e, b);
+    if (e->EB.acc) {
+      // AERO_F_EBNO: the estimator over the samples this launch consumed,
+      // while their AGC-ring entries and the ones EBNO_LEN behind are there
+      ev_begin(e, "ebno", a, b);
+      launch_ebno(e->st, e->EB, e->S, e->nch, cch ? 8400.0 : 10500.0);
+      ev_end(e, b);
+      e->ebno_launches++;
+    }
     if (int rc = note_consumed(e)) return rc;
     if (int rc = frame_round(e, flush, trace)) return rc;
     // with the DCD timer a channel's framing may stop at a tick that needs the
@@ -1357,7 +1411,7 @@ int group_create(aero_engine *E, int mode, int gid, int fs, std::unique_ptr<Grou
   if (hipMalloc(&e->pool, bytes) != hipSuccess) return AERO_E_NOMEM;
   e->pool_bytes = bytes;
   HIPCHK(hipMemset(e->pool, 0, bytes));
-  layout(e->S, e->T, mode, e->g, e->C, e->flags, reinterpret_cast<char *>(e->pool));
+  layout(e->S, e->T, mode, e->g, e->C, e->flags, reinterpret_cast<char *>(e->pool), nullptr, &e->EB);
   e->S.mg = mg;
   e->dcd_cont = e->S.dcd_cont != 0;
   HIPCHK(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
@@ -1888,6 +1942,7 @@ int group_add_channel(aero_engine *e, int gid, const aero_channel_cfg &cfg, int 
   g->infofield.emplace_back();
   g->soft_hold.emplace_back();
   g->hop_hold.emplace_back();
+  g->ebno_hold.emplace_back();
   g->pt_hold.emplace_back();
   g->blk_hold.emplace_back();
   g->frame_hold.emplace_back();
@@ -1927,6 +1982,7 @@ void release_slot(aero_engine *e, int gid, int c) {
   g->infofield[c].clear();
   g->soft_hold[c].clear();
   g->hop_hold[c].clear();
+  g->ebno_hold[c].clear();
   g->pt_hold[c].clear();
   g->blk_hold[c].clear();
   g->frame_hold[c].clear();
@@ -2824,8 +2880,15 @@ int aero_stat(aero_engine *e, const char *name, uint64_t *value) {
   uint64_t v = 0;
   const std::string n(name);
   if (n != "rt_tests" && n != "rt_packets" && n != "rt_pass_max" && n != "viterbi_jobs" && n != "frames" &&
-      n != "su_crc_ok" && n != "device_bytes" && n != "groups" && n != "slot_resets" && n != "slot_copies")
+      n != "su_crc_ok" && n != "device_bytes" && n != "groups" && n != "slot_resets" && n != "slot_copies" &&
+      n != "ebno_launches")
     return AERO_E_INVALID;
+  if (n == "ebno_launches") {  // launches of the Eb/N0 kernel (AERO_F_EBNO: one per demod launch of an OQPSK or C group)
+    for (auto &g : e->groups)
+      if (g) v += g->ebno_launches;
+    *value = v;
+    return AERO_OK;
+  }
   if (n == "slot_copies") {  // launches of the pack / unpack kernels (one per export or import and group)
     v = e->retired_copies + burst_stat(e->burst[0], 4) + burst_stat(e->burst[1], 4);
     for (auto &g : e->groups)
@@ -2935,6 +2998,49 @@ int aero_channel_get_events(aero_engine *e, int ch, aero_channel_events *out) {
     out->dcd_edges = g->dcd[c].edges;
   }
   return AERO_OK;
+}
+
+int aero_channel_get_quality(aero_engine *e, int ch, aero_channel_quality *out) {
+  if (!e || !out) return AERO_E_INVALID;
+  memset(out, 0, sizeof *out);
+  if (route_burst(e, ch) >= 0) return AERO_E_INVALID;  // burst channels report on another schedule
+  int c;
+  Group *g = route(e, ch, c);
+  if (!g) return AERO_E_INVALID;
+  HIPCHK(hipSetDevice(e->device));
+  if (int rc = flush_pending_init(g)) return rc;
+  // one counter and four doubles into pinned staging, one wait
+  long long *pl = reinterpret_cast<long long *>(g->pin_stat);
+  double *pd = reinterpret_cast<double *>(g->pin_stat) + 1;
+  const size_t C = (size_t)g->C;
+  const bool eb = g->EB.acc != nullptr;
+  HIPCHK(hipMemcpyAsync(pl, g->S.ls + (size_t)LS_NSAMP * C + c, 8, hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(pd, g->S.ds + (size_t)DS_MSE * C + c, 8, hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(pd + 1, g->S.ds + (size_t)DS_M2_FREQ * C + c, 8, hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(pd + 2, g->S.ds + (size_t)DS_MC_FREQ * C + c, 8, hipMemcpyDeviceToHost, g->st));
+  if (eb) HIPCHK(hipMemcpyAsync(pd + 3, g->EB.acc + 2 * C + c, 8, hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipStreamSynchronize(g->st));
+  // (hop records count from the channel's first sample, also over an MSK rate change)
+  out->samples = pl[0] + g->hop_base[c];
+  out->mse = pd[0];
+  out->mixer_hz = pd[1];
+  out->center_hz = pd[2];
+  // gotasignal of FreqOffsetEstimateSlot (coarse.hip hop_control): OQPSK and C 0.65, MSK 0.5
+  const double thr = (g->mode == MODE_OQPSK || g->mode == MODE_C8400) ? 0.65 : 0.5;
+  out->signal = !(out->mse > thr) ? 1 : 0;
+  out->ebno_valid = eb ? 1 : 0;
+  out->ebno_db = eb ? pd[3] : 0.0;
+  return AERO_OK;
+}
+
+int aero_pop_ebno(aero_engine *e, int ch, double *dst, size_t cap_records, size_t *n) {
+  int c;
+  Group *g = route(e, ch, c);  // (null for a burst channel)
+  if (!g || !g->EB.tr) return AERO_E_INVALID;
+  size_t k = 0;
+  int rc = pop_vec(g->ebno_hold[c], dst, cap_records * 2, &k);
+  if (n) *n = k / 2;
+  return rc;
 }
 
 uint64_t aero_samples_processed(aero_engine *e) {

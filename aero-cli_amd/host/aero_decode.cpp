@@ -256,6 +256,7 @@ struct Topic {
   bool live = true;               // still decoding (--no-signal-exit stops a topic)
   long long scans_seen = 0;       // SignalHunter full scans reported
   long long dcd_seen = 0, steps_seen = 0;  // status events logged
+  double audio_s = 0, quality_at = 0;  // AERO_EBNO: seconds of audio pushed, and when the next quality line is due
 };
 
 int main(int argc, char **argv) {
@@ -357,8 +358,15 @@ int main(int argc, char **argv) {
   // in the reference, a steady MSK carrier's DCD flaps
   const char *tick = getenv("AERO_DCD_TICK");
   const int tickv = tick ? atoi(tick) : 1;
+  // AERO_EBNO=<seconds>: the engine computes the reference's Eb/N0 estimate
+  // (AERO_F_EBNO; the reference computes it and shows it nowhere), and every
+  // that many seconds of a topic's audio one line per channel reports it with
+  // the demodulator's MSE and mixer frequency, at the level of the DCD lines
+  const char *ebno_env = getenv("AERO_EBNO");
+  const double ebno_period = ebno_env ? atof(ebno_env) : 0.0;
   const int eflags =
-      tickv == 0 ? 0 : (AERO_F_DCD_TICK | AERO_F_DCD_TICK_BURST | (tickv == 2 ? AERO_F_DCD_TICK_CONT : 0));
+      (tickv == 0 ? 0 : (AERO_F_DCD_TICK | AERO_F_DCD_TICK_BURST | (tickv == 2 ? AERO_F_DCD_TICK_CONT : 0))) |
+      (ebno_period > 0 ? AERO_F_EBNO : 0);
   aero_engine_cfg ecfg{dev ? atoi(dev) : 0, (int)topics.size(), eflags};
   if (int rc = aero_engine_create(&ecfg, &eng)) {
     AH_CRIT("Failed to create the MI355X demodulation engine: %s", aero_strerror(rc));
@@ -455,6 +463,23 @@ int main(int argc, char **argv) {
       t.steps_seen = ev.hunter_steps;
     }
   };
+  // AERO_EBNO: after a run, the topics whose audio has passed their next mark
+  // (aero_channel_get_quality waits for the channel's GPU work, so it is only
+  // asked then); burst channels have no such report
+  auto log_quality = [&]() {
+    if (!(ebno_period > 0)) return;
+    for (auto &t : topics) {
+      if (!t.live || t.audio_s < t.quality_at + ebno_period) continue;
+      while (t.audio_s >= t.quality_at + ebno_period) t.quality_at += ebno_period;
+      aero_channel_quality q;
+      if (aero_channel_get_quality(eng, t.ch, &q) != AERO_OK) continue;
+      if (q.ebno_valid)
+        AH_DBG("Signal quality: EbNo %.1f dB, MSE %.3f, mixer %.1f Hz%s", q.ebno_db, q.mse, q.mixer_hz,
+               tag(t).c_str());
+      else
+        AH_DBG("Signal quality: MSE %.3f, mixer %.1f Hz%s", q.mse, q.mixer_hz, tag(t).c_str());
+    }
+  };
   // SignalHunter::noSignalAfterScan -> handleNoSignalAfterFullScan
   // (decode/decode.cpp:418-427), polled about once a second
   long long last_check = 0;
@@ -527,6 +552,7 @@ int main(int argc, char **argv) {
             rc = aero_push_pcm(eng, t.ch, reinterpret_cast<const int16_t *>(samples.data()), bytes / 2, rate);
             tm.mark("push");
             tm.count("messages");
+            if (rc == AERO_OK && rate) t.audio_s += (double)(bytes / 2) / (double)rate;
             if (rc == AERO_E_RATE) {
               // the engine re-applies an MSK channel's settings at 12000,
               // 24000 or 48000 Hz (mskdemodulator.cpp:473-481); other rates
@@ -552,6 +578,7 @@ int main(int argc, char **argv) {
     tm.mark("run");
     drain();
     tm.mark("drain");
+    log_quality();
     check_scans();
     tm.mark("events");
     tm.count("batches");

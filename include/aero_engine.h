@@ -95,6 +95,27 @@ extern "C" {
                                   in the reference, a steady MSK carrier's DCD flaps
                                   under the timer.  OQPSK and burst channels ignore
                                   the flag */
+#define AERO_F_EBNO 0x200      /* continuous OQPSK and the C channel: compute the
+                                  reference's Eb/N0 estimate (OQPSKEbNoMeasure,
+                                  decode/DSP.cpp:691-722, fed once per sample from
+                                  OqpskDemodulator::writeData and emitted once per
+                                  coarse hop, decode/oqpskdemodulator.cpp:397-402,
+                                  :614) for aero_channel_get_quality, and with
+                                  AERO_F_TRACE_HOPS aero_pop_ebno.  One more kernel
+                                  after every demod launch of those groups reads
+                                  the estimator's 2 s of input back out of the AGC
+                                  ring the demodulator keeps anyway; its state is
+                                  three doubles and a counter per channel.  No
+                                  decoded output changes by one bit.  Without the
+                                  flag nothing is allocated or launched.  The state
+                                  is part of a channel's blob: the layout
+                                  fingerprint of an OQPSK or C channel differs with
+                                  the flag (and, with it, with AERO_F_TRACE_HOPS,
+                                  which adds the record ring), so such a blob moves
+                                  only between engines that agree on it
+                                  (aero_channel_import: AERO_E_INVALID otherwise).
+                                  Continuous MSK and burst channels ignore the
+                                  flag (aero_channel_quality says why) */
 
 typedef struct aero_engine aero_engine;
 
@@ -338,7 +359,8 @@ int aero_pop_c_units(aero_engine *e, int ch, uint8_t *dst, size_t cap, size_t *n
 int aero_pop_voice(aero_engine *e, int ch, uint8_t *dst, size_t cap, size_t *n);
 int aero_pop_rt_packets(aero_engine *e, int ch, uint8_t *dst, size_t cap, size_t *n);
 
-/* Timing (AERO_F_TIMING): kernel names {"demod","coarse","frame","viterbi"}
+/* Timing (AERO_F_TIMING): kernel names {"demod","coarse","frame","viterbi"},
+ * and with AERO_F_EBNO "ebno" (prefixed "c8400_" for the C group, as the others),
  * give summed device milliseconds (HIP events) and launch counts; host
  * sections {"host_push","host_run","host_wait_njobs","host_wait_jobs",
  * "host_frames"} give summed wall milliseconds and entry counts.  Both since
@@ -358,7 +380,8 @@ void aero_timing_reset(aero_engine *e);
  * host threads); "slot_copies": launches of the kernels that pack and unpack
  * exported / imported slots; "slot_resets": launches of the kernel that resets closed
  * channels' slots (one per group for all the slots closed since the group
- * last pushed or ran).  Joins the
+ * last pushed or ran); "ebno_launches": launches of the Eb/N0 kernel (0
+ * without AERO_F_EBNO).  Joins the
  * asynchronous host frame work first.  AERO_E_INVALID for another name. */
 int aero_stat(aero_engine *e, const char *name, uint64_t *value);
 
@@ -383,6 +406,48 @@ typedef struct {
   double hunter_fc[8];
 } aero_channel_events;
 int aero_channel_get_events(aero_engine *e, int ch, aero_channel_events *out);
+
+/* Signal quality of one continuous channel, for a host that ranks many VFOs
+ * of one engine (which of the opened channels hold a usable carrier, how good
+ * it is, when it degrades).  Waits for the channel's queued GPU work, as
+ * aero_channel_stat does.
+ *   samples    input samples demodulated since the channel opened
+ *   mse        the demodulator's mean squared error after `samples` samples
+ *              (what FreqOffsetEstimateSlot tests, oqpskdemodulator.cpp:562-620,
+ *              mskdemodulator.cpp:430-469)
+ *   mixer_hz   mixer2's frequency; center_hz the mixer centre
+ *   signal     1 when mse is not above the kind's threshold (0.65 for OQPSK
+ *              and C, 0.5 for MSK): what the hunter takes for "got a signal"
+ *   ebno_db    with AERO_F_EBNO on a continuous OQPSK or C channel
+ *              (ebno_valid = 1): OQPSKEbNoMeasure::EbNo after `samples`
+ *              samples, 0 .. 50 dB in the reference's own calibration.  The
+ *              reference never initialises EbNo; here it starts at 0.0 and
+ *              the 0.8 / 0.2 smoothing forgets the start within a few samples.
+ *              Otherwise ebno_valid = 0 and ebno_db = 0
+ * After a plain aero_run a channel stands on its last hop's boundary:
+ * samples, mse, mixer_hz, center_hz and signal then equal fields 0, 4, 2, 3
+ * and 5 of the last aero_pop_hops record bit for bit, and ebno_db is the value
+ * the reference emits with that hop (EbNoMeasurmentSignal).
+ *
+ * ebno_valid stays 0 for continuous MSK: MSKEbNoMeasure averages 2 s while the
+ * MSK AGC ring the estimate would be read from holds 1 s, so it would need a
+ * ring of its own of up to 192000 doubles per channel, carried over rate
+ * changes.  Burst channels emit their EbNo on another schedule (per burst):
+ * AERO_E_INVALID, as for a closed or out-of-range id. */
+typedef struct {
+  int64_t samples;
+  double ebno_db, mse, mixer_hz, center_hz;
+  int32_t signal, ebno_valid;
+} aero_channel_quality;
+int aero_channel_get_quality(aero_engine *e, int ch, aero_channel_quality *out);
+
+/* AERO_F_EBNO with AERO_F_TRACE_HOPS (parity tests): 2 doubles per record,
+ * (sample index, EbNo), in order; one record whenever a demod launch leaves
+ * the channel on a coarse-hop boundary, so every hop record popped so far has
+ * a record with its sample index (field 0), and a flush that ends exactly on a
+ * boundary may leave one more.  AERO_E_INVALID without both flags, and for
+ * continuous MSK and burst channels. */
+int aero_pop_ebno(aero_engine *e, int ch, double *dst, size_t cap_records, size_t *n);
 
 /* Total input samples demodulated across channels since creation. */
 uint64_t aero_samples_processed(aero_engine *e);

@@ -12,6 +12,7 @@
 
 #include "../aero-cli_amd/csrc/acars_host.h"
 #include "../aero-cli_amd/csrc/dcd_host.h"
+#include "../aero-cli_amd/csrc/ebno.h"
 #include "../aero-cli_amd/csrc/tables_host.h"
 
 extern "C" {
@@ -63,6 +64,19 @@ void hc_dcd_pass(int *state, unsigned long long syncs, const int *jobs, const un
   state[0] = d.cd;
   state[1] = d.dcd;
   state[2] = d.edges;
+}
+
+// The Eb/N0 kernel's walk (ebno.hip) in plain C++ over ebno.h's step, for one
+// channel whose AGC ring is `ring` (agc_len doubles, agc_ptr the pointer after
+// sample nsamp - 1): takes the samples [done, nsamp).  state: {s1, s2, EbNo},
+// updated.  Returns 0, or -1 for a span the ring no longer holds.
+int aero_x_ebno_run(const double *ring, int agc_len, int agc_ptr, long long done, long long nsamp, double fb,
+                    double *state) {
+  if (!ring || !state || agc_len < aero::EBNO_LEN || agc_ptr < 0 || agc_ptr >= agc_len || nsamp < done ||
+      nsamp - done > (long long)(agc_len - aero::EBNO_LEN))
+    return -1;
+  aero::ebno_walk(ring, 1, agc_len, agc_ptr, done, nsamp, fb, state);
+  return 0;
 }
 
 void hc_cis(double *cis) { aero::host_cis(cis); }
