@@ -240,9 +240,10 @@ __device__ __forceinline__ bool hop_control(HopCtl &h, std::integral_constant<in
 // time in the kernel over the workgroups that ran a hop (slot 10: less the
 // sections, the turnover between channels and the launch) and the number of
 // hops (slot 11).  With the overlapped head slots 0 and 1 count the plain
-// heads only and slot 2 the successor's mix; its ring words and image stores
-// run inside slot 6, its table gathers inside slot 7, the twiddle write and
-// the y stores inside slot 8 (scripts/coarse_stamps.py)
+// heads only and slot 2 the successor's mix; its image loads, the barrier
+// inside |X| and the issue of its table gathers run inside slot 6, the
+// twiddle write at the head of slot 7, under which the gathers land
+// (scripts/coarse_stamps.py)
 constexpr int CSTAMP_N = 12;
 #ifdef AERO_X_STAMPS
 __device__ unsigned long long g_cstamps[CSTAMP_N];
@@ -317,8 +318,8 @@ __device__ __forceinline__ HopEpi load_epi(const DevState &S, int C, int c) {
 
 // The workgroup's LDS (coarse_lds.h).  Without the overlapped head: the four
 // arrays as they always were.  With it: one raw buffer carved at the map's
-// offsets, because the next channel's ring image lies across the end of lds,
-// s_tw and the spare behind it.
+// offsets, because the next channel's ring image lies across the end of lds
+// and s_tw.
 template <int L, int YLEN, bool OVL>
 struct CoarseLds {
   double *lds;
@@ -399,11 +400,14 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
     // The overlapped head (OVL).  While the workgroup is in channel c's tail
     // and a due successor c' is left in the batch, it already runs c''s head:
     //   before the third transform   c''s HopPro
-    //   under |X|                    c''s ring words -> the image behind ylds
-    //   under the log10 loop         the image's words, bit-reversed, and
-    //                                the table gathers into x[] (dead since
-    //                                |X|), four elements per three iterations
-    //   after the loop's barrier     s_tw, which the image lay over, again
+    //   under the first half of |X|  c''s ring words -> the image behind ylds,
+    //                                by loads that write the LDS directly
+    //   a barrier inside |X|         the image is whole
+    //   under the second half        the image's words, bit-reversed, and the
+    //                                table gathers into x[] as its registers
+    //                                die
+    //   after the barrier of |X|     s_tw, which the image lay over, again
+    //   under the log10 loop         nothing of c' is issued; the gathers land
     //   after the fold's barrier     the mix, and c''s forward transform
     // pre says that x[] holds c''s snapshot already.  It follows from mask alone,
     // which every wave derives for itself from state that does not change
@@ -428,8 +432,9 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       const long long nk = (long long)K::HOPN * (hops_done + 1) - 1;
       // ring entry of the hop sample not written yet (the demod segment ended
       // before the sample was pushed): mixer_center has not moved since.  The
-      // word goes to the ring and, by the thread that copies its place, into
-      // the LDS image (not read back from memory).
+      // word goes to the ring and into the LDS image (not read back from
+      // memory): by the thread that copies its place in the plain head, by
+      // one thread of the wave that loaded its place in the overlapped one.
       // For a successor cc (overlapped head) this runs under its predecessor's
       // tail, before that channel's hop control: everything read here
       // (DS_MC_PTR, the PCM word, LS_FILLED through HopPro) is cc's own, which
@@ -579,33 +584,44 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       chain::fft<L, false, false>(x, t, lds, T.tw, s_tw, T.twg);
       CSTAMP(5);
       if constexpr (PERSIST) t = tnow();
-      // OVL: the successor's ring words, coalesced, on their way while the
-      // second half of |X| is computed (issued where half of x[] is dead:
-      // held through all of |X| they spilled)
-      uint32_t rw[16];
       uint32_t pcmw[8];  // the 16 PCM halves of the successor's ring words, two per register
       int fixjn = -1;
       uint32_t fixwn = 0;
       const long long nkn = (long long)K::HOPN * (pn.hops_done + 1) - 1;
       if (OVL && nxt) ring_fixup(cn, pn.filled, nkn, t, fixjn, fixwn);
       if constexpr (OVL) {
-        // no store in flight from here to the end of the log10 loop (lane 0's
-        // of the previous channel's hop control are long done, the fix-up's
-        // are rare): with a store possibly in flight the compiler takes the
+        // no store in flight from here to the end of |X| (lane 0's of the
+        // previous channel's hop control are long done, the fix-up's are
+        // rare): with a store possibly in flight the compiler takes the
         // counter to be out of order and turns every wait below into a wait
         // for everything, the gathers included
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
       }
-      auto ring_issue = [&]() {
+      // OVL: the successor's ring words go into the image (coarse_lds.h) by
+      // loads that write the LDS directly, no register between: wave w's
+      // i-th load brings words 64 w + lane + 1024 i to a wave-uniform place
+      // plus lane x 4.  The image lies behind ylds[0 .. ypad(YLEN - 1)],
+      // which the waves write during |X|, across the rest of lds and s_tw,
+      // short of red_* (the map's static_asserts).  This thread has passed
+      // the barrier that ends the third transform's exchange (chain::gx): by
+      // then every wave has finished its reads of the exchange and made the
+      // transform's last read of s_tw (stages <= 9, before the exchange).
+      // Called where no ordinary load's result is used before the wait in the
+      // middle of |X|: with such a load in flight the compiler makes the next
+      // use of any load's result a wait for everything
+      auto image_issue = [&]() {
         if constexpr (OVL) {
+          using LM = clds::Map<L, YLEN, OVL>;
           if (nxt) {
             const uint32_t *ringn = S.cring + (size_t)cn * N + fresh(t);
+            uint32_t *dst = sm.img + LM::img(wave * 64);
 #pragma unroll
-            for (int i = 0; i < N / FT; ++i) rw[i] = ringn[i * FT];
-          } else {
-            // (defined on this path too, or the words stay live around the walk)
-#pragma unroll
-            for (int i = 0; i < N / FT; ++i) rw[i] = 0;
+            for (int i = 0; i < N / FT; ++i) {
+              static_assert(LM::img(64 + 1024) == LM::img(64) + LM::img(1024), "the map adds over wave and load");
+              __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(ringn + i * FT),
+                                               (__attribute__((address_space(3))) void *)(dst + LM::img(i * FT)), 4, 0,
+                                               0);
+            }
           }
         }
       };
@@ -626,6 +642,16 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       auto yload = [&](int k) { return (k < YLEN && !yreset) ? yg[k] : 20.0; };
 #endif
       double yp0 = yload(t), yp1 = yload(t + FT);
+      // OVL: everything the tail loads before the gathers goes out ahead of
+      // the image loads and is back at the wait in the middle of |X|: the
+      // third look-ahead y value, and s_tw's entry for when the image is read
+      double yp2 = 0.0;
+      double2 twv = make_double2(0.0, 0.0);
+      if constexpr (OVL) {
+        yp2 = yload(t + 2 * FT);
+        twv = T.tw[min(t, TwLds<L>::LEN - 1)];
+        image_issue();
+      }
       // no barrier here: the third transform's workgroup exchange ended with
       // one (chain::gx), after which every wave only works in registers, so the
       // LDS is free for |X| as soon as this wave gets here
@@ -648,41 +674,119 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
         const double a = fabs(x[i].x), b = fabs(x[i].y);
         nr = nr && a <= 0x1p200 && b <= 0x1p200 && (a >= 0x1p-200 || b >= 0x1p-200);
       }
-      if (__all(nr)) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          if (i == 8) ring_issue();
-          const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
-          if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT_NR(x[i].x, x[i].y);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          if (i == 8) ring_issue();
-          const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
-          if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT(x[i].x, x[i].y);
-        }
-      }
-      if constexpr (OVL) {
-        // the image (coarse_lds.h): behind ylds[0 .. ypad(YLEN - 1)], which the
-        // other waves are writing, across the rest of lds, s_tw and the spare,
-        // short of red_* (the map's static_asserts).  No image write comes
-        // before the barrier that ends the third transform's exchange
-        // (chain::gx), which this thread has passed: by then every wave has
-        // finished its reads of the exchange (the image lies in lds behind
-        // ylds) and made the transform's last read of s_tw (stages <= 9,
-        // before the exchange).  The thread that copies the fix-up's place
-        // patches the word, as in the plain head
-        if (nxt) {
-          using LM = clds::Map<L, YLEN, OVL>;
-#pragma unroll
-          for (int i = 0; i < N / FT; ++i) {
-            const int j = t + i * FT;
-            sm.img[LM::img(j)] = j == fixjn ? fixwn : rw[i];
+      // OVL: element i of the successor's snapshot: its word from the image,
+      // bit-reversed as the plain head reads it, the PCM half packed and the
+      // table gather issued into x[i] (dead once its |X| is stored)
+      const long long s0n = nkn - (N - 1);
+      auto gather_word = [&](int i) {
+        using LM = clds::Map<L, YLEN, OVL>;
+        const int q = (int)((s0n + bitrev<L>(epos<L, 0>(t, i))) & (N - 1));
+        const uint32_t w = sm.img[LM::img(q)];
+        pcmw[i >> 1] |= (i & 1) ? (w & 0xFFFF0000u) : (w >> 16);
+#ifdef AERO_X_CISLINE
+        x[i] = T.cis[w & 0x7];  // timing build: every gather on one line
+#else
+        x[i] = T.cis[w & 0xFFFF];
+#endif
+      };
+      auto gather1 = [&](int i) {
+        if constexpr (OVL) {
+          if (nxt) {
+            gather_word(i);
+          } else {
+            // No successor: the same number of loads, of the table's entry 0,
+            // of which nothing comes.  x[] has to be defined on this path too
+            // (otherwise the previous values stay live around the whole
+            // walk), and with loads here as there the two paths join with the
+            // same loads in flight: joined with none in flight on this one,
+            // the compiler counts its waits for this path, and on the other
+            // they then wait for gathers just issued.  (One set of
+            // unconditional gathers with the index forced to 0 tipped the
+            // register allocation into spilling.)
+            x[i] = T.cis[0];
           }
         }
+      };
+      if constexpr (!OVL) {
+        if (__all(nr)) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
+            if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT_NR(x[i].x, x[i].y);
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
+            if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT(x[i].x, x[i].y);
+          }
+        }
+        yp2 = yload(t + 2 * FT);
+      } else {
+        // |X| in two halves with one barrier between them, outside the
+        // branch on the hypot path, so that every wave passes the same
+        // barriers whichever path it takes.
+        //   first half    registers 0 .. XH - 1, the image loads in flight
+        //   the barrier   every wave has waited for its own image loads
+        //                 (which orders them for its own LDS accesses) and,
+        //                 past the barrier, everybody's: the image is whole
+        //   second half   the successor's elements are gathered into x[] as
+        //                 the registers die: at once those of the first half
+        //                 and those no lane stores, then one after each |X|
+        // All image reads come before the barrier that closes |X|: past it
+        // s_tw, under the image, is written again.
+        constexpr int XH = 8;
+        using LM = clds::Map<L, YLEN, OVL>;
+        if (__all(nr)) {
+#pragma unroll
+          for (int i = 0; i < XH; ++i) {
+            if (!stored(i)) continue;
+            const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
+            if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT_NR(x[i].x, x[i].y);
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < XH; ++i) {
+            if (!stored(i)) continue;
+            const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
+            if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT(x[i].x, x[i].y);
+          }
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's image loads have landed
+        // the fix-up's word is not in memory yet when the image loads read its
+        // place (or may not be): the thread whose wave loaded the place
+        // patches the image, after that wave's loads
+        if (nxt && fixjn >= 0 && (fixjn & (FT - 1)) == t) sm.img[LM::img(fixjn)] = fixwn;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pcmw[k] = 0;
+        // (one branch around the whole group: its words are read together)
+        if (nxt) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (i < XH || !stored(i)) gather_word(i);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (i < XH || !stored(i)) gather1(i);
+        }
+        // (the hypot path is chosen per register here, the gathers outside
+        // the choice: around one branch over the whole half the compiler
+        // waited in the branch-free path's first hypot for every gather of
+        // the group above)
+        const bool allnr = __all(nr);
+#pragma unroll
+        for (int i = XH; i < 16; ++i) {
+          if (!stored(i)) continue;
+          const int yi = (bin_t | chain::out_bin_reg<L>(i)) ^ (N / 2);
+          if (allnr) {
+            if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT_NR(x[i].x, x[i].y);
+          } else {
+            if (yi >= K::YLO && yi <= K::YHI) ylds[ypad(yi - K::YLO)] = CO_HYPOT(x[i].x, x[i].y);
+          }
+          gather1(i);
+        }
       }
-      double yp2 = yload(t + 2 * FT);
       __syncthreads();
       CSTAMP(6);
       // the loads that would otherwise sit between two channels, issued here
@@ -696,19 +800,38 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       // gathered table entries do not fit beside the loop together)
       HopEpi ep{};
       if (PERSIST && !OVL && t < 64) ep = load_epi(S, C, c);
-      double2 twv;
+      // OVL: the log10 loop as eleven written-out iterations with the y store
+      // inside (AERO_X_YWRITTEN 2, what is built).  Timing builds: 0, the
+      // plain head's form (rolled, the y store inside), whose first iteration
+      // waits for every gather; 1, written out with the y stores in a pass of
+      // their own under the fold.  Stamps and bench of the three: DESIGN.md §4
+#ifndef AERO_X_YWRITTEN
+#define AERO_X_YWRITTEN 2
+#endif
+      constexpr bool YWRITTEN = OVL && AERO_X_YWRITTEN != 0;
+      constexpr bool YSTORE_PASS = YWRITTEN && AERO_X_YWRITTEN == 1;  // 2: the y store inside the iterations
+      if constexpr (OVL) {
+        // every wave has read the image (the barrier above): s_tw, which it
+        // covered, is written again from the table load_tw_lds read it from
+        // (entry j by thread j, as there), so bit for bit what it was; the
+        // fold's closing barrier publishes it before any wave starts the
+        // successor's forward transform.  (From the table and not saved in
+        // registers: a saved entry would have to be read before the third
+        // transform's exchange and live through it, where the kernel's
+        // register peak is, or cost a barrier of its own before the image.)
+        if (nxt && t < TwLds<L>::LEN) s_tw[t] = twv;
+      }
       auto ycalc = [&](double yold, int k) {
         // OVL: log's table from LDS.  From memory, each lookup is a vector-
         // memory load the iteration waits for, and with it (loads count down
-        // in issue order) for every table gather issued before it
+        // in issue order) for every table gather still in flight before it
         double lg;
         if constexpr (OVL)
           lg = CO_LOG10_GE1_TAB(fmax(ylds[ypad(k)], 1.0), sm.logtab);
         else
           lg = CO_LOG10_GE1(fmax(ylds[ypad(k)], 1.0));
         const double ynew = yold * 0.9 + 0.1 * 10 * lg;
-        // OVL: to memory after the loop, from ylds (ystore below)
-        if constexpr (!OVL) yg[k] = ynew;
+        yg[k] = ynew;
         ylds[ypad(k)] = ynew;
       };
       auto ybody = [&](int k) {
@@ -718,62 +841,15 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
         yp2 = yload(k + 3 * FT);
         ycalc(yold, k);
       };
-      // OVL: elements i0 .. i0 + 3 of the successor's snapshot: their words
-      // from the image, bit-reversed as the plain head reads them, the PCM
-      // halves packed and the table gathers issued into x[] (dead since |X|)
-      const long long s0n = nkn - (N - 1);
-      auto gather4 = [&](auto i0c) {
-        if constexpr (OVL) {
-          using LM = clds::Map<L, YLEN, OVL>;
-          constexpr int i0 = decltype(i0c)::value;
-          if (nxt) {
-#pragma unroll
-            for (int i = i0; i < i0 + 4; ++i) {
-              const int q = (int)((s0n + bitrev<L>(epos<L, 0>(t, i))) & (N - 1));
-              const uint32_t w = sm.img[LM::img(q)];
-              pcmw[i >> 1] = (i & 1) ? (pcmw[i >> 1] | (w & 0xFFFF0000u)) : (w >> 16);
-#ifdef AERO_X_CISLINE
-              x[i] = T.cis[w & 0x7];  // timing build: every gather on one line
-#else
-              x[i] = T.cis[w & 0xFFFF];
-#endif
-            }
-          } else {
-            // No successor: the same number of loads, of the table's entry 0,
-            // of which nothing comes.  x[] and pcmw[] have to be defined on
-            // this path too (otherwise the previous values stay live around
-            // the whole walk), and with loads here as there the two paths
-            // join with the same loads in flight: joined with none in flight
-            // on this one, the compiler counted the iterations' waits for
-            // this path, and on the other they then waited for gathers just
-            // issued.  (One set of unconditional gathers with the index
-            // forced to 0 tipped the register allocation into spilling.)
-#pragma unroll
-            for (int i = i0; i < i0 + 4; ++i) {
-              x[i] = T.cis[0];
-              pcmw[i >> 1] = 0;
-            }
-          }
-        }
-      };
-      if constexpr (OVL) {
-        // The gathers under the log10 loop.  A wave's vector-memory loads
-        // count down in issue order, so a y load issued after a gather is not
-        // usable before that gather is back: the gathers go four elements at
-        // a time ahead of three iterations each, and every iteration's
-        // look-ahead y load is used three iterations on, by when the four
-        // gathers before it have long returned.  The iterations are written
-        // out: a rolled loop moves the look-ahead values from register to
-        // register at its top, which waits for the youngest of them and with
-        // it for every gather in flight.
-        // For the same reason the loop stores nothing to memory: with stores
-        // and loads both in flight the counter tells nothing about either, and
-        // every wait becomes a wait for all.  The new y goes to ylds as always
-        // and from there to memory after the loop (ystore).
-        // All image reads come before the barrier below: past it other waves
-        // write s_tw again, under the image.
-        static_assert((YLEN + FT - 1) / FT <= 12, "four groups of three iterations cover the bins");
-        twv = make_double2(0.0, 0.0);
+      if constexpr (YWRITTEN) {
+        // The written-out form: no copy of a look-ahead value from register
+        // to register, which waits for the youngest load and with it for
+        // every gather still in flight.  The first three iterations use the
+        // history values that came back inside |X| and wait for nothing; the
+        // fourth uses the first look-ahead load issued here, behind the
+        // gathers, which have three iterations more to land.  The y store
+        // inside the iterations keeps the waits counted (vmcnt(2), what the
+        // compiler emits), so the store pass under the fold is gone.
         // One iteration, yp holding y[k] on entry and y[k + 3 FT] after.  The
         // old value is used up (0.9 y) before the new one is asked for, so
         // that the load can land in the same register: a loaded value handed
@@ -802,16 +878,16 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
 #endif
               const double lg = CO_LOG10_GE1_TAB(fmax(ylds[ypad(in ? k : YLEN - 1)], 1.0), sm.logtab);
               const double ynew = a + 0.1 * 10 * lg;
-              if (in) ylds[ypad(k)] = ynew;
+              if (in) {
+                ylds[ypad(k)] = ynew;
+                if constexpr (!YSTORE_PASS) yg[k] = ynew;
+              }
             }
           }
         };
+        static_assert(NIT <= 12, "four groups of three iterations cover the bins");
         auto ygroup = [&](auto i0c) {
           constexpr int g = decltype(i0c)::value / 4;
-          // s_tw's entry, for after the barrier: ahead of the last gathers,
-          // so that waiting for it does not wait for them
-          if (g == 3) twv = T.tw[min(t, TwLds<L>::LEN - 1)];
-          gather4(i0c);
           ystep(yp0, std::integral_constant<int, 3 * g>());
           ystep(yp1, std::integral_constant<int, 3 * g + 1>());
           ystep(yp2, std::integral_constant<int, 3 * g + 2>());
@@ -827,18 +903,11 @@ __global__ __launch_bounds__(1 << (CoarseK<M>::LOG2N - 4), CoarseK<M>::LOG2N == 
       __syncthreads();
       CSTAMP(7);
       if constexpr (OVL) {
-        // every wave has read the image (the barrier above): s_tw, which it
-        // covered, is written again from the table load_tw_lds read it from
-        // (entry j by thread j, as there), so bit for bit what it was; the
-        // fold's closing barrier publishes it before any wave starts the
-        // successor's forward transform.  (From the table and not saved in
-        // registers: a saved entry would have to be read before the third
-        // transform's exchange and live through it, where the kernel's
-        // register peak is, or cost a barrier of its own before the image.)
-        if (nxt && t < TwLds<L>::LEN) s_tw[t] = twv;
-        // ystore: this thread's new y values, from ylds to memory
+        if constexpr (YSTORE_PASS) {
+          // ystore: this thread's new y values, from ylds to memory
 #pragma unroll 1
-        for (int k = t; k < YLEN; k += FT) yg[k] = ylds[ypad(k)];
+          for (int k = t; k < YLEN; k += FT) yg[k] = ylds[ypad(k)];
+        }
         if (t < 64) ep = load_epi(S, C, c);
       }
       // fold search (coarsefreqestimate.cpp:119-140): first strict maximum above 0

@@ -9,15 +9,20 @@
  *           image, and in a hop's tail ylds (|X| and y of the bins the fold
  *           reads) in its first YSPAN doubles
  *   s_tw    TWLEN double2: the forward twiddles of the stages served from LDS
- *   spare   what the overlapped head's image needs beyond s_tw
+ *   spare   what the overlapped head's image needs beyond s_tw (nothing, as
+ *           the image is placed now)
  *   red_v, red_i   the fold's per-wave maxima
  *   logtab  (overlapped head only) log's 128-pair table
  *
  * The overlapped head (persistent 16384-point kinds) keeps the next
- * channel's ring image (uint32 words, one pad word per 16 as in the plain
- * head) in the hop's tail behind ylds: over the rest of lds, all of s_tw
- * (which the kernel writes again from the twiddle table once the image is
- * read, thread j entry j) and the spare.
+ * channel's ring image (uint32 words, one pad word per 64) in the hop's tail
+ * behind ylds: over the rest of lds and all of s_tw (which the kernel writes
+ * again from the twiddle table once the image is read, thread j entry j),
+ * ending where s_tw ends.  The image is filled by loads that write the LDS
+ * directly: one wave-load puts its 64 words at a wave-uniform base plus
+ * lane x 4, so the 64 words of a wave-load (ring words 64 w + lane + 1024 i)
+ * are contiguous; the pad word per 64 keeps the bit-reversed read (words 16
+ * apart across a wave's lanes) on 64 different banks.
  *
  * Plain constexpr arithmetic only: compiled for the device and for the host.
  */
@@ -42,13 +47,18 @@ struct Map {
   static constexpr int YSPAN = ypad(YLEN - 1) + 1;
   static constexpr int Y_BYTES = YSPAN * 8;
   // the image: word j of the ring at uint32 img(j) from IMG_OFF
-  static constexpr int img(int j) { return j + (j >> 4); }
-  static constexpr int IMG_WORDS = img(N - 1) + 1;
-  static constexpr int IMG_OFF = Y_BYTES, IMG_BYTES = IMG_WORDS * 4, IMG_END = IMG_OFF + IMG_BYTES;
+  static constexpr int img(int j) { return j + (j >> 6); }
+  // the map before the image was filled by direct loads (one pad word per 16,
+  // as the plain head's image in lds has): kept for the map's tests
+  static constexpr int img16(int j) { return j + (j >> 4); }
+  static constexpr int IMG_WORDS = img(N - 1) + 1, IMG_BYTES = IMG_WORDS * 4;
 
   static constexpr int LDS_OFF = 0, LDS_BYTES = PADDED * 8;
   static constexpr int TW_OFF = LDS_OFF + LDS_BYTES, TW_BYTES = TWLEN * 16;
   static constexpr int SPARE_OFF = TW_OFF + TW_BYTES;
+  // the image ends where s_tw ends (it covers s_tw whole), as far behind
+  // ylds as that allows
+  static constexpr int IMG_OFF = SPARE_OFF - IMG_BYTES, IMG_END = IMG_OFF + IMG_BYTES;
   static constexpr int SPARE_BYTES = !OVL || IMG_END <= SPARE_OFF ? 0 : (IMG_END - SPARE_OFF + 7) / 8 * 8;
   static constexpr int REDV_OFF = SPARE_OFF + SPARE_BYTES, REDV_BYTES = FT / 64 * 8;
   static constexpr int REDI_OFF = REDV_OFF + REDV_BYTES, REDI_BYTES = FT / 64 * 4;

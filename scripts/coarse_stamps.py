@@ -35,12 +35,12 @@ vout = (ctypes.c_ulonglong * 4)()
 # With the overlapped head (the default; AERO_COARSE_OVERLAP=0 for the plain one) a channel that
 # follows another in its batch has no head of its own: slots 0 and 1 then count the plain heads
 # only (a batch's first due channel), slot 2 the serial rest (the successor's mix), and the
-# successor's ring words and image stores run inside slot 6, its table gathers inside slot 7, the
-# twiddle write and the y stores inside slot 8.  What the other waves
+# successor's image loads, the barrier inside |X| and the issue of its table gathers run inside
+# slot 6, the twiddle write at the head of slot 7, under which the gathers land.  What the other waves
 # wait for lane 0's hop control shows in wave 0's figures only as the kernel time per hop.
 names = ['batch scan + state (plain heads)', 'ring to LDS (plain heads)', 'gathers + mix / serial mix', 'FFT 1',
-         'boxcar+iFFT+square', 'FFT 3', 'hypot + next ring image', 'log10 + next gathers',
-         'fold + twiddles, y stores', 'hop control (lane 0)']
+         'boxcar+iFFT+square', 'FFT 3', 'hypot + next image, gathers', 'twiddles + log10',
+         'fold', 'hop control (lane 0)']
 order = list(range(10))
 for s in range(steps):
     views = [pool[:, int(o) + s * 4096:int(o) + (s + 1) * 4096] for o in offs]

@@ -39,3 +39,35 @@ extern "C" void coarse_lds_image(int *off) {
 
 // byte offset of y bin q's double in ylds
 extern "C" int coarse_lds_ybin(int q) { return 8 * clds::ypad(q); }
+
+// The image as the kernel fills it: wave w's i-th direct-to-LDS load brings
+// ring words 64 w + lane + 1024 i.  word[lane], off[lane]: the ring word each
+// lane loads and the byte offset of its place (tests/test_coarse_lds_map_dma.py)
+extern "C" void coarse_lds_image_waveload(int w, int i, int *word, int *off) {
+  for (int lane = 0; lane < 64; ++lane) {
+    const int j = 64 * w + lane + Ovl::FT * i;
+    word[lane] = j;
+    off[lane] = Ovl::IMG_OFF + 4 * Ovl::img(j);
+  }
+}
+
+namespace {
+int bitrev14(int p) {
+  int r = 0;
+  for (int b = 0; b < L; ++b) r |= ((p >> b) & 1) << (L - 1 - b);
+  return r;
+}
+}  // namespace
+
+// The gather's read of the image: thread t = 64 w + lane reads, for its
+// element i of a snapshot that starts at sample s0, ring word
+// q = (s0 + bitrev14(16 t + i)) & (N - 1).  off[lane]: the byte offset read,
+// in this map (old_map = 0) or in the map the image had when it was written
+// through registers, one pad word per 16 (old_map = 1), from the same base
+extern "C" void coarse_lds_image_read(int w, int i, int s0, int old_map, int *off) {
+  for (int lane = 0; lane < 64; ++lane) {
+    const int t = 64 * w + lane;
+    const int q = (s0 + bitrev14(16 * t + i)) & (Ovl::N - 1);
+    off[lane] = Ovl::IMG_OFF + 4 * (old_map ? Ovl::img16(q) : Ovl::img(q));
+  }
+}
