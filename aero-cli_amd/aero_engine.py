@@ -34,7 +34,8 @@ F_DCD_TICK = 0x40  # AeroL's 1 s DCD timer on the sample clock (continuous OQPSK
 F_DCD_TICK_BURST = 0x80  # the timer on burst channels: a tick at the end of the message that completes a second
 F_DCD_TICK_CONT = 0x100  # the timer on continuous MSK and C channels, on the sample clock (their DCD can fall)
 F_EBNO = 0x200  # continuous OQPSK / C: the reference's Eb/N0 estimate (channel_quality, pop_ebno)
-F_TRACE_ALL = F_TRACE_PT | F_TRACE_BLOCKS | F_TRACE_SOFT | F_TRACE_HOPS | F_TRACE_FRAMES
+F_EBNO_MSK = 0x400  # continuous MSK 600 / 1200 at any rate: MSKEbNoMeasure, with a 2 Fs ring per channel
+F_TRACE_ALL =F_TRACE_PT | F_TRACE_BLOCKS | F_TRACE_SOFT | F_TRACE_HOPS | F_TRACE_FRAMES
 
 MATH_FN = {'hypot': 0, 'atan2': 1, 'tanh': 2, 'sin': 3, 'cos': 4, 'log10': 5, 'sqrt': 6, 'fmod360': 7,
            'div': 8, 'div_c48000': 9, 'div_c360': 10, 'div_n': 11, 'div_c192000': 13, 'hypot_nr': 14, 'atan2_bf': 15,
@@ -533,7 +534,7 @@ class Engine:
         """aero_stat counter: 'viterbi_jobs', 'frames', 'su_crc_ok' (and burst 'rt_*'), or the
         continuous groups' 'device_bytes' / 'groups', 'slot_resets' (reset-kernel launches),
         'slot_copies' (pack / unpack launches of export_channels / import_channels) or
-        'ebno_launches' (launches of the Eb/N0 kernel, F_EBNO)."""
+        'ebno_launches' (launches of the Eb/N0 kernels, F_EBNO / F_EBNO_MSK)."""
         v = ctypes.c_uint64()
         _check(self.lib.aero_stat(self.h, name.encode(), ctypes.byref(v)), 'aero_stat')
         return int(v.value)
@@ -555,14 +556,16 @@ class Engine:
 
     def channel_quality(self, ch):
         """aero_channel_get_quality: dict of samples, ebno_db, mse, mixer_hz, center_hz, signal,
-        ebno_valid (ebno_db only with F_EBNO on a continuous OQPSK or C channel)."""
+        ebno_valid (ebno_db only with F_EBNO on a continuous OQPSK or C channel, 0 .. 50 dB, or with
+        F_EBNO_MSK on a continuous MSK channel, (-inf, 50] dB and negative during the first 2 s)."""
         q = ChannelQuality()
         _check(self.lib.aero_channel_get_quality(self.h, ch, ctypes.byref(q)), 'aero_channel_get_quality')
         return dict(samples=int(q.samples), ebno_db=q.ebno_db, mse=q.mse, mixer_hz=q.mixer_hz,
                     center_hz=q.center_hz, signal=int(q.signal), ebno_valid=int(q.ebno_valid))
 
     def ebno(self, ch):
-        """aero_pop_ebno: [n, 2] (sample index, EbNo) per hop boundary reached (F_EBNO | F_TRACE_HOPS)."""
+        """aero_pop_ebno: [n, 2] (sample index, EbNo) per hop boundary reached (F_TRACE_HOPS with F_EBNO,
+        or with F_EBNO_MSK on a continuous MSK channel)."""
         return self._pop(self.lib.aero_pop_ebno, ch, np.float64, 2)
 
     def samples_processed(self):

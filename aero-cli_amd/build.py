@@ -5,6 +5,7 @@
   oracle/liboracle.so              test-only CPU restatement (checker)
   tools/liboracle_tick.so          the same plus a DCD-timer hook (checker of the burst and continuous-MSK timers)
   tools/liboracle_ebno.so          the same plus the reference's Eb/N0 estimator restated (checker of AERO_F_EBNO)
+  tools/liboracle_ebno_msk.so      the same plus MSKEbNoMeasure restated (checker of AERO_F_EBNO_MSK)
   tools/liboracle_ranges.so        the same with its observation hook defined (range probe; built by its tests)
 
 Usage: python aero-cli_amd/build.py [--engine] [--synth] [--oracle] [-j N]
@@ -239,6 +240,24 @@ def build_oracleebno():
     return ORACLEEBNO_SO
 
 
+ORACLEEBNOMSK_SO = os.path.join(ROOT, 'tools', 'liboracle_ebno_msk.so')
+
+
+def build_oracleebnomsk():
+    """Test-only: the oracle as it stands plus a plain restatement of the reference's
+    MSKEbNoMeasure fed from the oracle's MSK AGC buffer (tools/oracle_ebno_msk.cpp;
+    tests/ebno_msk_lib.py), the checker of AERO_F_EBNO_MSK.  build_oracleebno()'s flags."""
+    src = os.path.join(ROOT, 'tools', 'oracle_ebno_msk.cpp')
+    deps = [src] + [os.path.join(ORACLE_DIR, f) for f in ('aero_oracle.cpp', 'pub_oracle.cpp', 'aero_oracle.h')]
+    if _stale(ORACLEEBNOMSK_SO, deps):
+        tmp = '%s.%d.tmp' % (ORACLEEBNOMSK_SO, os.getpid())  # renamed into place: never loaded half written
+        _run(['g++', '-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Wextra',
+              '-Wno-subobject-linkage', '-Wl,-Bsymbolic', '-shared', '-o', tmp, src,
+              os.path.join(ORACLE_DIR, 'pub_oracle.cpp'), '-lm'])
+        os.replace(tmp, ORACLEEBNOMSK_SO)
+    return ORACLEEBNOMSK_SO
+
+
 ORACLERANGES_SO = os.path.join(ROOT, 'tools', 'liboracle_ranges.so')
 
 
@@ -354,6 +373,7 @@ def build_all(jobs=4):
     build_oracle()
     build_oracletick()
     build_oracleebno()
+    build_oracleebnomsk()
     build_synth()
     build_mathhost()
     build_fftsim()

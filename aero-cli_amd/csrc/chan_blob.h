@@ -34,7 +34,7 @@ constexpr uint32_t BLOB_VERSION = 1;
 constexpr size_t BLOB_HEADER = 48;
 // flags that shape what a channel decodes or what its slot holds
 constexpr uint32_t BLOB_FLAGS = AERO_F_TRACE_PT | AERO_F_TRACE_BLOCKS | AERO_F_DCD_TICK | AERO_F_DCD_TICK_BURST |
-                                AERO_F_DCD_TICK_CONT;
+                                AERO_F_DCD_TICK_CONT | AERO_F_EBNO_MSK;
 
 // appends little-endian fields to a string
 struct BlobWriter {

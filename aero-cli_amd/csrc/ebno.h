@@ -96,7 +96,106 @@ AERO_HD void ebno_walk(const double *ring, long long stride, int agc_len, int ag
   state[2] = eb;
 }
 
-// device arrays of a flagged OQPSK or C group (engine.hip layout())
+// ---------------------------------------------------------------- MSK
+// The estimator of a continuous MSK demodulator (AERO_F_EBNO_MSK):
+// MSKEbNoMeasure::Update (decode/DSP.cpp:487-503) on two MovingAverage(2 Fs)
+// (decode/DSP.cpp:409-417), constructed as MSKEbNoMeasure(2.0 * Fs)
+// (decode/mskdemodulator.cpp:36) and again by every setSettings (:138-140), fed
+// dabval once per sample (:305-309) and emitted once per coarse hop, before
+// the hop sample's own Update (:461 through :72-76, :287-296).
+//
+// Its input is again what AGC::Update stores as fabs(sig), but the MSK AGC is
+// AGC(1, Fs): the ring S.agc[Fs][C] holds one second and the window is two.
+// So the estimator keeps a ring of its own, time-major [2 Fs][C], of its last
+// 2 Fs inputs: sample i (counted from the estimator's construction) is read
+// from the AGC ring's row i % Fs, the term E drops is the own ring's row
+// i % (2 Fs) (0.0 while i < 2 Fs, as the zeroed ring gives it) and the term E2
+// drops is that entry times itself (the argument above), and the sample then
+// takes that row.  EbNo is never initialised by the reference
+// (decode/DSP.cpp:482-485); it starts at 0.0 here, at open and after every
+// rate change (a reset slot of the new rate's group).
+//
+// There is no lower clamp: EbNo is negative while the window fills, and a
+// tebno of -inf (a log argument of +inf) leaves EbNo at -inf for good.
+
+// MASum / (double)MASz for MASz = 2 Fs = len, a group constant and no literal,
+// so div_c (whose reciprocal the compiler folds) does not serve.  Its sequence
+// does, with rlen = RN(1 / len) taken once per launch by the IEEE division:
+// Markstein's theorem asks of the divisor only that rlen is its correctly
+// rounded reciprocal, and len is an integer in [24000, 192000], normal with a
+// normal reciprocal (a power of two, 32768 .. 131072, makes q0 exact and the
+// correction zero).  The numerator is div_cw's: behind a wave-uniform test
+// that it is zero or at least 2^-900 in magnitude, which keeps the quotient by
+// at most 192000 normal and the residual exact; the sums of a carrier that went
+// away are cancellation residues of any size, and a wave that holds a smaller
+// one takes the IEEE division.  The sums cannot overflow (at most 192000 terms
+// below 2^4 and their squares).
+AERO_HD double msk_ebno_div(double a, double len, double rlen) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (__builtin_expect(__all(in_div_cw(a)), 1)) {
+    const double q0 = a * rlen;
+    const double q = fma(fma(-len, q0, a), rlen, q0);
+    return a == 0.0 ? q0 : q;
+  }
+#else
+  (void)rlen;
+#endif
+  return a / len;
+}
+
+// The sample's tebno from the two sums (decode/DSP.cpp:490-500); lg2 is
+// aero_log10(2.0), glibc's log10(2.0) bit for bit, taken once per launch.
+// sqrt(2) / Mean is the IEEE division: silence gives a zero mean (alpha = inf,
+// Var alpha = 0 inf = NaN -> 50), a carrier that went away a residue mean of
+// any size and sign, so no contract on the divisor holds.  aero_log10 sees
+// whatever Var alpha^2 - 0.0085 is: negative (NaN -> 50), zero (-inf -> +inf
+// -> 50), +inf (-> tebno -inf, which stays), and subnormals never (the
+// subtraction of 0.0085 leaves none), though the function handles them.
+AERO_HD double msk_ebno_tebno(double s1, double s2, double len, double rlen, double lg2) {
+  const double v2 = msk_ebno_div(s2, len, rlen);    // E2->Val
+  const double mean = msk_ebno_div(s1, len, rlen);  // E->Val = Mean
+  const double var = v2 - mean * mean;
+  const double alpha = 1.4142135623730951 / mean;  // sqrt(2) / Mean
+  double t = 10.0 * (lg2 - aero_log10(((var * alpha) * alpha) - 0.0085)) - 5.0;
+  if (t != t) t = 50;  // std::isnan
+  if (t > 50.0) t = 50;
+  return t;
+}
+
+// MSKEbNoMeasure::Update (the sums and the recurrence are the OQPSK ones)
+AERO_HD double msk_ebno_step(double &s1, double &s2, double ebno, double a, double old, double len, double rlen,
+                             double lg2) {
+  ebno_sums(s1, s2, a, old);
+  return ebno_smooth(ebno, msk_ebno_tebno(s1, s2, len, rlen, lg2));
+}
+
+// The walk of one channel over the samples [done, nsamp) counted from the
+// estimator's construction: `agc` the AGC ring (fs rows, `astride` doubles
+// between rows, sample i at row i % fs), `own` the estimator's ring (2 fs
+// rows, `ostride` between rows), updated.  Needs nsamp - done <= fs (the
+// samples' AGC entries not yet overwritten).  state: {s1, s2, EbNo}.
+// ebno.hip's kernel does the same with the tebno evaluations of four samples
+// side by side; tools/hostcheck.cpp runs this one.
+AERO_HD void msk_ebno_walk(const double *agc, long long astride, double *own, long long ostride, int fs,
+                           long long done, long long nsamp, double *state) {
+  double s1 = state[0], s2 = state[1], eb = state[2];
+  const int len = 2 * fs;
+  const double dlen = (double)len, rlen = 1.0 / dlen, lg2 = aero_log10(2.0);
+  int ar = (int)(done % fs), row = (int)(done % len);
+  for (long long i = done; i < nsamp; ++i) {
+    const double a = agc[(long long)ar * astride];
+    eb = msk_ebno_step(s1, s2, eb, a, own[(long long)row * ostride], dlen, rlen, lg2);
+    own[(long long)row * ostride] = a;
+    ar = ar + 1 == fs ? 0 : ar + 1;
+    row = row + 1 == len ? 0 : row + 1;
+  }
+  state[0] = s1;
+  state[1] = s2;
+  state[2] = eb;
+}
+
+// device arrays of a flagged OQPSK or C group, or (AERO_F_EBNO_MSK, with a ring
+// of its own beside them) of a continuous MSK group (engine.hip layout())
 struct EbnoDev {
   double *acc;      // [3][C] s1, s2, EbNo
   long long *done;  // [C] samples the estimator has taken

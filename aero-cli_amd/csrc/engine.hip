@@ -71,6 +71,7 @@ void upload_c_constants(const DelayDesc *);
 int c_prejob_bytes();
 // ebno.hip
 void launch_ebno(hipStream_t, const EbnoDev &, const DevState &, int, double);
+void launch_ebno_msk(hipStream_t, const EbnoDev &, double *, const DevState &, int);
 // slot_reset.hip
 void launch_reset_slots(hipStream_t, void *, const ResetSeg *, int, const int *, const int *, int, const ResetInit *,
                         unsigned long long);
@@ -87,6 +88,9 @@ constexpr int HOP_CAP = 64;
 // AERO_F_EBNO: after a demod launch the AGC ring still holds the launch's samples and the
 // entries EBNO_LEN behind them, which the estimator's moving averages drop (ebno.h)
 static_assert(PCM_CAP <= AGC_LEN - EBNO_LEN, "a demod launch must not outrun the Eb/N0 estimator's window in the AGC ring");
+// AERO_F_EBNO_MSK: an MSK demod launch ends at the next hop boundary at the latest (run_pass), and
+// the AGC ring of the slowest group (AGC(1, Fs), Fs rows) still holds every sample of such a launch
+static_assert(MSK_HOP <= MSK_FS_MIN, "an MSK demod launch must not outrun the AGC ring its Eb/N0 estimator reads");
 
 #define HIPCHK(x)                                   \
   do {                                              \
@@ -243,7 +247,10 @@ struct Group {
   // AERO_F_EBNO on an OQPSK or C group (ebno.hip): the estimator's device
   // arrays (null without the flag), its launches (aero_stat "ebno_launches"),
   // and with AERO_F_TRACE_HOPS the (sample index, EbNo) records collected
+  // AERO_F_EBNO_MSK on a continuous MSK group: the same arrays, and the
+  // estimator's own ring eb_ring[2 Fs][C] (the MSK AGC ring holds 1 s of its 2 s)
   EbnoDev EB{};
+  double *eb_ring = nullptr;
   uint64_t ebno_launches = 0;
   std::vector<std::vector<double>> ebno_hold;
   std::vector<std::vector<uint8_t>> blk_hold, frame_hold;
@@ -399,7 +406,7 @@ namespace {
 // notes in `rec` how a channel's part of it is addressed: the per-channel
 // entries are the reset plan of a slot (group_reset_plan, aero_x_reset_plan).
 size_t layout(DevState &S, DevTables &T, int mode, const ModeGeom &g, int C, int flags, char *base,
-              LayoutRec *rec = nullptr, EbnoDev *EB = nullptr) {
+              LayoutRec *rec = nullptr, EbnoDev *EB = nullptr, double **eb_ring = nullptr) {
   const bool msk = mode != MODE_OQPSK && mode != MODE_C8400;
   char *p = base;
   if (rec) rec->C = C;
@@ -492,10 +499,18 @@ size_t layout(DevState &S, DevTables &T, int mode, const ModeGeom &g, int C, int
   // AERO_F_TRACE_HOPS the per-hop records.  Per-channel arrays like the rest:
   // the reset plan, the pack / unpack kernels and the fingerprint cover them.
   // Without the flag nothing is carved and the pool is what it was.
+  // AERO_F_EBNO_MSK (continuous MSK, fixed and generic rates): the same, and
+  // MSKEbNoMeasure's last 2 Fs inputs, time-major [2 Fs][C] (16 Fs bytes per
+  // channel: the MSK AGC ring holds one of the window's two seconds, ebno.h).
+  // A channel that changes rate lands in a reset slot of the new rate's
+  // group: zero sums, EbNo, done-count and ring, which is the estimator
+  // setSettings constructs (decode/mskdemodulator.cpp:138-140).
   EbnoDev eb{};
-  if (!msk && (flags & AERO_F_EBNO)) {
+  double *ring = nullptr;
+  if (msk ? (flags & AERO_F_EBNO_MSK) != 0 : (flags & AERO_F_EBNO) != 0) {
     col(eb.acc, 3);
     col(eb.done, 1);
+    if (msk) col(ring, (size_t)2 * g.fs);
     if (flags & AERO_F_TRACE_HOPS) {
       eb.tr_cap = HOP_CAP;
       row(eb.tr, (size_t)HOP_CAP * 2);
@@ -503,6 +518,7 @@ size_t layout(DevState &S, DevTables &T, int mode, const ModeGeom &g, int C, int
     }
   }
   if (EB) *EB = eb;
+  if (eb_ring) *eb_ring = ring;
   return (size_t)(p - base);
 }
 
@@ -900,7 +916,11 @@ int collect_traces(Group *e) {
         if (n <= 0) continue;
         const double *src = h.data() + (rows ? 0 : (size_t)c * rec);
         if (rows) HIPCHK(hipMemcpy(h.data(), e->EB.tr + (size_t)c * rec, (size_t)n * 2 * 8, hipMemcpyDeviceToHost));
-        e->ebno_hold[c].insert(e->ebno_hold[c].end(), src, src + (size_t)n * 2);
+        auto &eh = e->ebno_hold[c];
+        const size_t at = eh.size();
+        eh.insert(eh.end(), src, src + (size_t)n * 2);
+        if (e->hop_base[c])  // MSK after a rate change: the index counts from the channel's first sample
+          for (size_t r = at; r < eh.size(); r += 2) eh[r] += (double)e->hop_base[c];
       }
       HIPCHK(hipMemset(e->EB.tr_n, 0, sizeof(int) * nch));
     }
@@ -1173,9 +1193,13 @@ int run_pass(Group *e, int flush, bool *more) {
     ev_end(e, b);
     if (e->EB.acc) {
       // AERO_F_EBNO: the estimator over the samples this launch consumed,
-      // while their AGC-ring entries and the ones EBNO_LEN behind are there
+      // while their AGC-ring entries and the ones EBNO_LEN behind are there;
+      // AERO_F_EBNO_MSK: over the at most one hop of samples, into its own ring
       ev_begin(e, "ebno", a, b);
-      launch_ebno(e->st, e->EB, e->S, e->nch, cch ? 8400.0 : 10500.0);
+      if (e->eb_ring)
+        launch_ebno_msk(e->st, e->EB, e->eb_ring, e->S, e->nch);
+      else
+        launch_ebno(e->st, e->EB, e->S, e->nch, cch ? 8400.0 : 10500.0);
       ev_end(e, b);
       e->ebno_launches++;
     }
@@ -1411,7 +1435,7 @@ int group_create(aero_engine *E, int mode, int gid, int fs, std::unique_ptr<Grou
   if (hipMalloc(&e->pool, bytes) != hipSuccess) return AERO_E_NOMEM;
   e->pool_bytes = bytes;
   HIPCHK(hipMemset(e->pool, 0, bytes));
-  layout(e->S, e->T, mode, e->g, e->C, e->flags, reinterpret_cast<char *>(e->pool), nullptr, &e->EB);
+  layout(e->S, e->T, mode, e->g, e->C, e->flags, reinterpret_cast<char *>(e->pool), nullptr, &e->EB, &e->eb_ring);
   e->S.mg = mg;
   e->dcd_cont = e->S.dcd_cont != 0;
   HIPCHK(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
@@ -2120,6 +2144,11 @@ int msk_migrate(aero_engine *e, int ch, uint32_t fs) {
   std::swap(h->infofield[c2], g->infofield[c]);
   std::swap(h->soft_hold[c2], g->soft_hold[c]);
   std::swap(h->hop_hold[c2], g->hop_hold[c]);
+  // AERO_F_EBNO_MSK: the records not yet popped move too.  The estimator does
+  // not: the flush above gave the old one every sample of the old rate, and the
+  // new slot's zeroed sums, EbNo, ring and done-count (which restarts with
+  // LS_NSAMP) are the estimator setSettings constructs: nothing is copied
+  std::swap(h->ebno_hold[c2], g->ebno_hold[c]);
   std::swap(h->pt_hold[c2], g->pt_hold[c]);
   std::swap(h->blk_hold[c2], g->blk_hold[c]);
   std::swap(h->frame_hold[c2], g->frame_hold[c]);
@@ -2883,7 +2912,7 @@ int aero_stat(aero_engine *e, const char *name, uint64_t *value) {
       n != "su_crc_ok" && n != "device_bytes" && n != "groups" && n != "slot_resets" && n != "slot_copies" &&
       n != "ebno_launches")
     return AERO_E_INVALID;
-  if (n == "ebno_launches") {  // launches of the Eb/N0 kernel (AERO_F_EBNO: one per demod launch of an OQPSK or C group)
+  if (n == "ebno_launches") {  // launches of the Eb/N0 kernel (AERO_F_EBNO: one per demod launch of an OQPSK or C group; AERO_F_EBNO_MSK: of a continuous MSK group)
     for (auto &g : e->groups)
       if (g) v += g->ebno_launches;
     *value = v;

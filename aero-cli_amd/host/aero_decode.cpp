@@ -359,14 +359,15 @@ int main(int argc, char **argv) {
   const char *tick = getenv("AERO_DCD_TICK");
   const int tickv = tick ? atoi(tick) : 1;
   // AERO_EBNO=<seconds>: the engine computes the reference's Eb/N0 estimate
-  // (AERO_F_EBNO; the reference computes it and shows it nowhere), and every
+  // (AERO_F_EBNO, and AERO_F_EBNO_MSK for the 600 / 1200 topics; the reference
+  // computes it and shows it nowhere), and every
   // that many seconds of a topic's audio one line per channel reports it with
   // the demodulator's MSE and mixer frequency, at the level of the DCD lines
   const char *ebno_env = getenv("AERO_EBNO");
   const double ebno_period = ebno_env ? atof(ebno_env) : 0.0;
   const int eflags =
       (tickv == 0 ? 0 : (AERO_F_DCD_TICK | AERO_F_DCD_TICK_BURST | (tickv == 2 ? AERO_F_DCD_TICK_CONT : 0))) |
-      (ebno_period > 0 ? AERO_F_EBNO : 0);
+      (ebno_period > 0 ? (AERO_F_EBNO | AERO_F_EBNO_MSK) : 0);
   aero_engine_cfg ecfg{dev ? atoi(dev) : 0, (int)topics.size(), eflags};
   if (int rc = aero_engine_create(&ecfg, &eng)) {
     AH_CRIT("Failed to create the MI355X demodulation engine: %s", aero_strerror(rc));

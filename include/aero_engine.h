@@ -116,6 +116,34 @@ extern "C" {
                                   (aero_channel_import: AERO_E_INVALID otherwise).
                                   Continuous MSK and burst channels ignore the
                                   flag (aero_channel_quality says why) */
+#define AERO_F_EBNO_MSK 0x400  /* continuous 600/1200-bps MSK at any rate in
+                                  [12000, 96000] Hz (the compiled 12 / 24 / 48 kHz
+                                  groups, the generic-rate groups, both kernel
+                                  shapes): compute the reference's Eb/N0 estimate
+                                  (MSKEbNoMeasure, decode/DSP.cpp:482-503, fed
+                                  dabval once per sample and emitted once per
+                                  coarse hop, decode/mskdemodulator.cpp:305-309,
+                                  :461) for aero_channel_get_quality, and with
+                                  AERO_F_TRACE_HOPS aero_pop_ebno.  The estimator
+                                  averages 2 s and the MSK AGC ring holds 1 s, so
+                                  each channel keeps a ring of its own of 2 Fs
+                                  doubles: 16 Fs bytes per channel slot of the
+                                  group (192 KB at 12 kHz, 1.5 MB at 96 kHz; a
+                                  full 65536-channel 12 kHz group 12.6 GB), in
+                                  aero_stat("device_bytes").  One more kernel runs
+                                  after every demod launch of those groups.  No
+                                  MSK demod kernel and no decoded output changes.
+                                  A rate change starts a fresh estimator, as the
+                                  reference's setSettings constructs one
+                                  (:138-140).  Without the flag nothing is
+                                  allocated or launched, and layouts and blobs
+                                  are what they were.  The flag is one of a
+                                  blob's decode-shaping flags: a blob moves only
+                                  between engines that agree on it
+                                  (aero_channel_import: AERO_E_INVALID otherwise).
+                                  OQPSK, C and burst channels ignore it;
+                                  AERO_F_EBNO alone still leaves MSK without an
+                                  estimate */
 
 typedef struct aero_engine aero_engine;
 
@@ -360,7 +388,8 @@ int aero_pop_voice(aero_engine *e, int ch, uint8_t *dst, size_t cap, size_t *n);
 int aero_pop_rt_packets(aero_engine *e, int ch, uint8_t *dst, size_t cap, size_t *n);
 
 /* Timing (AERO_F_TIMING): kernel names {"demod","coarse","frame","viterbi"},
- * and with AERO_F_EBNO "ebno" (prefixed "c8400_" for the C group, as the others),
+ * and with AERO_F_EBNO / AERO_F_EBNO_MSK "ebno" (prefixed "c8400_" for the C
+ * group and "msk600_", "msk600_18750_", ... for an MSK group, as the others),
  * give summed device milliseconds (HIP events) and launch counts; host
  * sections {"host_push","host_run","host_wait_njobs","host_wait_jobs",
  * "host_frames"} give summed wall milliseconds and entry counts.  Both since
@@ -381,7 +410,7 @@ void aero_timing_reset(aero_engine *e);
  * exported / imported slots; "slot_resets": launches of the kernel that resets closed
  * channels' slots (one per group for all the slots closed since the group
  * last pushed or ran); "ebno_launches": launches of the Eb/N0 kernel (0
- * without AERO_F_EBNO).  Joins the
+ * without AERO_F_EBNO and AERO_F_EBNO_MSK).  Joins the
  * asynchronous host frame work first.  AERO_E_INVALID for another name. */
 int aero_stat(aero_engine *e, const char *name, uint64_t *value);
 
@@ -423,17 +452,28 @@ int aero_channel_get_events(aero_engine *e, int ch, aero_channel_events *out);
  *              samples, 0 .. 50 dB in the reference's own calibration.  The
  *              reference never initialises EbNo; here it starts at 0.0 and
  *              the 0.8 / 0.2 smoothing forgets the start within a few samples.
+ *              With AERO_F_EBNO_MSK on a continuous MSK channel
+ *              (ebno_valid = 1): MSKEbNoMeasure::EbNo after `samples`
+ *              samples, of the estimator constructed at the channel's last
+ *              rate change (`samples` itself counts from the channel's first
+ *              sample).  Range (-inf, 50] dB: the reference has no lower
+ *              clamp, so the value is negative during the first 2 s while
+ *              the window fills, and a sample whose log argument is +inf
+ *              leaves it at -inf until the next rate change.  It starts at
+ *              0.0 at open and after every rate change.
  *              Otherwise ebno_valid = 0 and ebno_db = 0
  * After a plain aero_run a channel stands on its last hop's boundary:
  * samples, mse, mixer_hz, center_hz and signal then equal fields 0, 4, 2, 3
  * and 5 of the last aero_pop_hops record bit for bit, and ebno_db is the value
  * the reference emits with that hop (EbNoMeasurmentSignal).
  *
- * ebno_valid stays 0 for continuous MSK: MSKEbNoMeasure averages 2 s while the
- * MSK AGC ring the estimate would be read from holds 1 s, so it would need a
- * ring of its own of up to 192000 doubles per channel, carried over rate
- * changes.  Burst channels emit their EbNo on another schedule (per burst):
- * AERO_E_INVALID, as for a closed or out-of-range id. */
+ * Continuous MSK has its estimate under a flag of its own because of what it
+ * costs: MSKEbNoMeasure averages 2 s while the MSK AGC ring holds 1 s, so each
+ * channel keeps a ring of 2 Fs doubles (up to 192000) for it; AERO_F_EBNO alone
+ * leaves ebno_valid = 0 there.  Burst channels compute their EbNo inside the
+ * burst demodulators, only while a burst is demodulated and from a value no
+ * ring keeps (per burst, another schedule): AERO_E_INVALID, as for a closed or
+ * out-of-range id. */
 typedef struct {
   int64_t samples;
   double ebno_db, mse, mixer_hz, center_hz;
@@ -441,12 +481,15 @@ typedef struct {
 } aero_channel_quality;
 int aero_channel_get_quality(aero_engine *e, int ch, aero_channel_quality *out);
 
-/* AERO_F_EBNO with AERO_F_TRACE_HOPS (parity tests): 2 doubles per record,
+/* AERO_F_EBNO (OQPSK, C) or AERO_F_EBNO_MSK (continuous MSK) with
+ * AERO_F_TRACE_HOPS (parity tests): 2 doubles per record,
  * (sample index, EbNo), in order; one record whenever a demod launch leaves
  * the channel on a coarse-hop boundary, so every hop record popped so far has
- * a record with its sample index (field 0), and a flush that ends exactly on a
- * boundary may leave one more.  AERO_E_INVALID without both flags, and for
- * continuous MSK and burst channels. */
+ * a record with its sample index (field 0, which counts across an MSK rate
+ * change as the hop records do), and a flush that ends exactly on a
+ * boundary may leave one more.  Records not yet popped follow an MSK channel
+ * to its new rate's group.  AERO_E_INVALID without both flags of the
+ * channel's kind, and for burst channels. */
 int aero_pop_ebno(aero_engine *e, int ch, double *dst, size_t cap_records, size_t *n);
 
 /* Total input samples demodulated across channels since creation. */

@@ -79,6 +79,19 @@ int aero_x_ebno_run(const double *ring, int agc_len, int agc_ptr, long long done
   return 0;
 }
 
+// The MSK Eb/N0 kernel's walk (ebno.hip ebno_msk_kernel) over ebno.h's step,
+// for one channel at rate fs: `agc` its AGC ring (fs doubles, sample i at
+// i % fs), `own` the estimator's ring (2 fs doubles, updated); takes the samples
+// [done, nsamp) counted from the estimator's construction.  state: {s1, s2,
+// EbNo}, updated.  Returns 0, or -1 for a span the AGC ring no longer holds.
+int aero_x_ebno_msk_run(const double *agc, double *own, int fs, long long done, long long nsamp, double *state) {
+  if (!agc || !own || !state || fs < 1 || done < 0 || nsamp < done || nsamp - done > (long long)fs) return -1;
+  aero::msk_ebno_walk(agc, 1, own, 1, fs, done, nsamp, state);
+  return 0;
+}
+// aero_log10(2.0), the constant of the MSK step (glibc's log10(2.0) bit for bit)
+double aero_x_ebno_msk_lg2(void) { return aero::aero_log10(2.0); }
+
 void hc_cis(double *cis) { aero::host_cis(cis); }
 void hc_twiddles(int nfft, double *tw, double *twi) { aero::host_twiddles(nfft, tw, twi); }
 int hc_rrc(double alpha, int firsize, double fs, double symfreq, double *pts) {
