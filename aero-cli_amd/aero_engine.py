@@ -103,6 +103,18 @@ class SurveyPeak(ctypes.Structure):
                 ('frequency', ctypes.c_longlong), ('first_bin', ctypes.c_int), ('last_bin', ctypes.c_int)]
 
 
+class ChanSurveyHoldCfg(ctypes.Structure):
+    _fields_ = [('group', ctypes.c_int), ('rows', ctypes.c_int), ('level', ctypes.c_void_p)]
+
+
+class SurveyAct(ctypes.Structure):
+    _fields_ = [('on_ratio', ctypes.c_double), ('off_ratio', ctypes.c_double), ('duty', ctypes.c_double),
+                ('kind', ctypes.c_int)]
+
+
+SURVEY_IDLE, SURVEY_CONTINUOUS, SURVEY_BURST = 0, 1, 2
+
+
 class ChannelEvents(ctypes.Structure):
     _fields_ = [('dcd_edges', ctypes.c_int64), ('hunter_steps', ctypes.c_int64), ('hunter_fc', ctypes.c_double * 8)]
 
@@ -208,6 +220,15 @@ _SIGS = {
     'aero_survey_peaks': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
                                          ctypes.POINTER(SurveyPeakCfg), ctypes.POINTER(SurveyPeak), ctypes.c_size_t,
                                          ctypes.POINTER(ctypes.c_size_t)]),
+    'aero_chan_survey_hold_start': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ChanSurveyHoldCfg)]),
+    'aero_chan_survey_hold_stop': (ctypes.c_int, [ctypes.c_void_p]),
+    'aero_chan_survey_hold_read': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    'aero_chan_survey_hold_rows': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t)]),
+    'aero_survey_activity': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                            ctypes.POINTER(SurveyPeak), ctypes.c_size_t, ctypes.POINTER(SurveyAct)]),
 }
 
 _lib = None
@@ -831,7 +852,7 @@ class Channeliser:
 
     def stat(self, name):
         """aero_chan_stat: 'device_bytes', 'vfo_inits' (start-kernel launches), 'slots_free',
-        'survey_launches' or 'survey_segments'."""
+        'survey_launches', 'survey_segments' or 'survey_groups'."""
         v = ctypes.c_uint64()
         _check(self.lib.aero_chan_stat(self.h, name.encode(), ctypes.byref(v)), 'aero_chan_stat')
         return int(v.value)
@@ -866,6 +887,47 @@ class Channeliser:
                'aero_chan_survey_read')
         return out, int(seg.value)
 
+    # ---- peak / min hold, duty and waterfall beside the survey
+    def survey_hold_start(self, group, rows=0, level=None):
+        """Starts a hold beside the survey that is on: groups of `group` consecutive segments from
+        the next segment completed; per bin the largest and smallest group sum, with `level`
+        (float64[N], natural bin order) the number of group sums above it, and with rows > 0 a
+        ring of the last `rows` group sums."""
+        n = getattr(self, '_survey_n', 0)
+        if level is not None:
+            level = np.ascontiguousarray(level, dtype=np.float64)
+            if level.shape != (n,):
+                raise ValueError('the level holds %d values' % n)
+        cfg = ChanSurveyHoldCfg(int(group), int(rows), level.ctypes.data if level is not None else None)
+        _check(self.lib.aero_chan_survey_hold_start(self.h, ctypes.byref(cfg)), 'aero_chan_survey_hold_start')
+        self._hold_rows = int(rows)
+
+    def survey_hold_stop(self):
+        _check(self.lib.aero_chan_survey_hold_stop(self.h), 'aero_chan_survey_hold_stop')
+
+    def survey_hold_read(self, reset=False):
+        """(peak float64[N], low float64[N], busy uint32[N], groups) after the runs launched so far;
+        reset=True then sets them back to +0, +inf, 0 and 0 (the unfinished group goes on)."""
+        n = getattr(self, '_survey_n', 1 << 14)
+        peak, low, busy = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.uint32)
+        g = ctypes.c_uint64()
+        _check(self.lib.aero_chan_survey_hold_read(self.h, peak.ctypes.data, low.ctypes.data, busy.ctypes.data, n,
+                                                   ctypes.byref(g), int(bool(reset))), 'aero_chan_survey_hold_read')
+        return peak, low, busy, int(g.value)
+
+    def survey_hold_rows(self, cap_rows=None):
+        """(the last group sums as float64[n][N], oldest first; the first one's group index).  A
+        cap_rows below the rows held returns the newest cap_rows (AERO_E_FULL is not an error here)."""
+        n = getattr(self, '_survey_n', 1 << 14)
+        cap = getattr(self, '_hold_rows', 0) if cap_rows is None else int(cap_rows)
+        out = np.zeros((max(cap, 1), n), dtype=np.float64)
+        first, got = ctypes.c_uint64(), ctypes.c_size_t()
+        rc = self.lib.aero_chan_survey_hold_rows(self.h, out.ctypes.data, cap, ctypes.byref(first), ctypes.byref(got))
+        if rc not in (AERO_OK, AERO_E_FULL):
+            raise AeroError(rc, 'aero_chan_survey_hold_rows')
+        self.hold_rows_full = rc == AERO_E_FULL
+        return out[:got.value], int(first.value)
+
 
 def survey_peaks(power, log2n, sample_rate, center, mix_offset=0, threshold=8.0, min_bins=2, merge_gap=2):
     """aero_survey_peaks (host only, no GPU): the carriers in a survey spectrum as dicts with
@@ -885,3 +947,26 @@ def survey_peaks(power, log2n, sample_rate, center, mix_offset=0, threshold=8.0,
     _check(lib.aero_survey_peaks(*args, out, n.value, ctypes.byref(n)), 'aero_survey_peaks')
     return [dict(offset_hz=p.offset_hz, bandwidth_hz=p.bandwidth_hz, ratio=p.ratio, frequency=int(p.frequency),
                  first_bin=p.first_bin, last_bin=p.last_bin) for p in out[:n.value]]
+
+
+def survey_activity(power, segments, peak, low, busy, groups, group, log2n, threshold, runs):
+    """aero_survey_activity (host only, no GPU): per run of survey_peaks (dicts with first_bin and
+    last_bin) a dict with on_ratio, off_ratio, duty (-1.0 when busy is None) and kind (SURVEY_IDLE,
+    SURVEY_CONTINUOUS or SURVEY_BURST)."""
+    lib = load_library()
+    n = 1 << int(log2n) if 0 <= int(log2n) <= 30 else 0
+    arr = []
+    for a, t in ((power, np.float64), (peak, np.float64), (low, np.float64), (busy, np.uint32)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=t)
+            if 2 <= int(log2n) <= 24 and a.shape != (n,):
+                raise ValueError('the arrays hold %d values' % n)
+        arr.append(a)
+    pk = (SurveyPeak * max(1, len(runs)))()
+    for p, r in zip(pk, runs):
+        p.first_bin, p.last_bin = int(r['first_bin']), int(r['last_bin'])
+    out = (SurveyAct * max(1, len(runs)))()
+    _check(lib.aero_survey_activity(arr[0].ctypes.data, int(segments), arr[1].ctypes.data, arr[2].ctypes.data,
+                                    arr[3].ctypes.data if arr[3] is not None else None, int(groups), int(group),
+                                    int(log2n), float(threshold), pk, len(runs), out), 'aero_survey_activity')
+    return [dict(on_ratio=o.on_ratio, off_ratio=o.off_ratio, duty=o.duty, kind=o.kind) for o in out[:len(runs)]]

@@ -379,7 +379,7 @@ struct aero_chan {
   uint64_t vfo_inits = 0;
   // wideband carrier survey (survey.hip): nullptr while none is on
   aero::Survey *survey = nullptr;
-  uint64_t survey_launches = 0, survey_segments = 0;
+  uint64_t survey_launches = 0, survey_segments = 0, survey_groups = 0;
 };
 
 namespace {
@@ -693,10 +693,11 @@ int run_impl(aero_chan *c) {
     hipLaunchKernelGGL(dc_kernel, dim3(1), dim3(64), 0, c->st, c->in, (long long)nb * c->B, c->avept);
   if (c->survey) {  // the stream the main VFOs read
     int nl = 0;
-    uint64_t ns = 0;
-    if (int rc = aero::survey_run(c->survey, c->st, c->in, (long long)nb * c->B, &nl, &ns)) return rc;
+    uint64_t ns = 0, ng = 0;
+    if (int rc = aero::survey_run(c->survey, c->st, c->in, (long long)nb * c->B, &nl, &ns, &ng)) return rc;
     c->survey_launches += (uint64_t)nl;
     c->survey_segments += ns;
+    c->survey_groups += ng;
   }
   for (int sd = 0; sd < 2; sd++) {
     if (!mix[sd].empty()) {
@@ -1153,6 +1154,8 @@ int aero_chan_stat(aero_chan *c, const char *name, uint64_t *value) {
     *value = c->survey_launches;
   else if (!strcmp(name, "survey_segments"))
     *value = c->survey_segments;
+  else if (!strcmp(name, "survey_groups"))
+    *value = c->survey_groups;
   else
     return AERO_E_INVALID;
   return AERO_OK;
@@ -1172,7 +1175,7 @@ int aero_chan_survey_stop(aero_chan *c) {
   CHK(hipSetDevice(c->cfg.device));
   if (int rc = run_impl(c)) return rc;  // the reads taken so far run with it
   CHK(hipStreamSynchronize(c->st));
-  c->dev_bytes -= aero::survey_bytes(c->survey);
+  c->dev_bytes -= aero::survey_bytes(c->survey) + aero::survey_hold_bytes(c->survey);  // a hold ends with it
   aero::survey_destroy(c->survey);
   c->survey = nullptr;
   return AERO_OK;
@@ -1182,6 +1185,39 @@ int aero_chan_survey_read(aero_chan *c, double *power, size_t cap, uint64_t *seg
   if (!c || !c->survey) return AERO_E_INVALID;
   CHK(hipSetDevice(c->cfg.device));
   return aero::survey_read(c->survey, c->st, power, cap, segments, reset);
+}
+
+int aero_chan_survey_hold_start(aero_chan *c, const aero_chan_survey_hold_cfg *cfg) {
+  if (!c || !cfg || !c->survey || aero::survey_hold_on(c->survey) || cfg->group < 1 || cfg->group > 65536 ||
+      cfg->rows < 0 || cfg->rows > 4096)
+    return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  if (int rc = run_impl(c)) return rc;  // the reads taken so far run without it
+  if (int rc = aero::survey_hold_start(c->survey, cfg->group, cfg->rows, cfg->level)) return rc;
+  c->dev_bytes += aero::survey_hold_bytes(c->survey);
+  return AERO_OK;
+}
+
+int aero_chan_survey_hold_stop(aero_chan *c) {
+  if (!c || !aero::survey_hold_on(c->survey)) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  CHK(hipStreamSynchronize(c->st));
+  c->dev_bytes -= aero::survey_hold_bytes(c->survey);
+  aero::survey_hold_stop(c->survey);
+  return AERO_OK;
+}
+
+int aero_chan_survey_hold_read(aero_chan *c, double *peak, double *low, uint32_t *busy, size_t cap, uint64_t *groups,
+                               int reset) {
+  if (!c || !aero::survey_hold_on(c->survey)) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  return aero::survey_hold_read(c->survey, c->st, peak, low, busy, cap, groups, reset);
+}
+
+int aero_chan_survey_hold_rows(aero_chan *c, double *dst, size_t cap_rows, uint64_t *first_group, size_t *n) {
+  if (!c || !aero::survey_hold_on(c->survey)) return AERO_E_INVALID;
+  CHK(hipSetDevice(c->cfg.device));
+  return aero::survey_hold_rows(c->survey, c->st, dst, cap_rows, first_group, n);
 }
 
 }  // extern "C"

@@ -23,6 +23,12 @@
  * second's worth), survey_threshold and survey_min_bins run the channeliser's
  * carrier survey and log one INFO line per carrier and period:
  *   survey: carrier <frequency> Hz bandwidth <Hz> Hz ratio <x> vfo <[vfos] id or ->
+ * With survey_hold_group (segments per group; absent or 0: off, ignored with
+ * a warning without survey_log2n) a peak / min hold runs beside it, and every
+ * report adds, behind its carrier lines, one INFO line per carrier that the
+ * hold saw in bursts (aero_survey_peaks on the hold's peak spectrum, then
+ * aero_survey_activity):
+ *   survey: burst <frequency> Hz bandwidth <Hz> Hz on <x.x> off <x.x> vfo <[vfos] id or ->
  */
 #include <execinfo.h>
 #include <signal.h>
@@ -275,6 +281,24 @@ int main(int argc, char **argv) {
     }
     survey_power.resize(n);
   }
+  // peak / min hold beside it: survey_hold_group segments per group, no level and no ring
+  const int hold_group = ini.value_int("survey_hold_group");
+  std::vector<double> hold_peak, hold_low;
+  std::vector<aero_survey_peak> hold_found(64);
+  std::vector<aero_survey_act> hold_act;
+  if (hold_group && survey_power.empty()) {
+    AH_WARN("survey_hold_group=%d ignored: survey_log2n is off", hold_group);
+  } else if (hold_group) {
+    const aero_chan_survey_hold_cfg hc{hold_group, 0, nullptr};
+    if (int rc = aero_chan_survey_hold_start(chan, &hc)) {
+      AH_CRIT("[ERROR] survey_hold_group=%d: %s (1 .. 65536)", hold_group, aero_strerror(rc));
+      fclose(src);
+      aero_chan_destroy(chan);
+      return 1;
+    }
+    hold_peak.resize(survey_power.size());
+    hold_low.resize(survey_power.size());
+  }
   const Zmq *z = zmq_load();
   if (!z) return 1;
   void *ctx = z->ctx_new();
@@ -381,17 +405,50 @@ int main(int argc, char **argv) {
         break;
       }
       const double binw = (double)Fs / (double)survey_power.size(), half = (double)(survey_power.size() / 2);
-      for (size_t k = 0; k < np; k++) {
-        const aero_survey_peak &p = survey_found[k];
-        // the [vfos] entry whose frequency lies inside the carrier's band
+      // the [vfos] entry whose frequency lies inside the carrier's band
+      auto vfo_of = [&](const aero_survey_peak &p) {
         std::string id = "-";
         for (size_t v = 0; v < vfos.size() && id == "-"; v++) {
           const double off = (double)vfos[v].frequency + (double)mix_offset - (double)center;
           if (off >= ((double)p.first_bin - half - 0.5) * binw && off <= ((double)p.last_bin - half + 0.5) * binw)
             id = std::to_string(v);
         }
+        return id;
+      };
+      for (size_t k = 0; k < np; k++) {
+        const aero_survey_peak &p = survey_found[k];
         AH_INF("survey: carrier %lld Hz bandwidth %.0f Hz ratio %.1f vfo %s", p.frequency, p.bandwidth_hz, p.ratio,
-               id.c_str());
+               vfo_of(p).c_str());
+      }
+      if (!hold_peak.empty()) {  // the carriers of the period's peak spectrum that were not on all the time
+        uint64_t groups = 0;
+        size_t nh = 0;
+        rc = aero_chan_survey_hold_read(chan, hold_peak.data(), hold_low.data(), nullptr, hold_peak.size(), &groups, 1);
+        if (!rc && segs && groups) {
+          rc = aero_survey_peaks(hold_peak.data(), survey_log2n, Fs, center, mix_offset, &peak_cfg, hold_found.data(),
+                                 hold_found.size(), &nh);
+          if (rc == AERO_E_FULL) {
+            hold_found.resize(nh);
+            rc = aero_survey_peaks(hold_peak.data(), survey_log2n, Fs, center, mix_offset, &peak_cfg, hold_found.data(),
+                                   hold_found.size(), &nh);
+          }
+          hold_act.resize(nh + 1);
+          if (!rc)
+            rc = aero_survey_activity(survey_power.data(), segs, hold_peak.data(), hold_low.data(), nullptr, groups,
+                                      hold_group, survey_log2n, peak_cfg.threshold, hold_found.data(), nh,
+                                      hold_act.data());
+        }
+        if (rc) {
+          AH_CRIT("survey hold error: %s", aero_strerror(rc));
+          rc_exit = 1;
+          break;
+        }
+        for (size_t k = 0; k < nh; k++) {
+          if (hold_act[k].kind != AERO_SURVEY_BURST) continue;
+          const aero_survey_peak &p = hold_found[k];
+          AH_INF("survey: burst %lld Hz bandwidth %.0f Hz on %.1f off %.1f vfo %s", p.frequency, p.bandwidth_hz,
+                 hold_act[k].on_ratio, hold_act[k].off_ratio, vfo_of(p).c_str());
+        }
       }
       tm.mark("survey");
     }

@@ -156,10 +156,11 @@ int aero_chan_vfo_count(aero_chan *c, int *n);
  * always there: 124 (Hilbert) + audio taps + ceil(late taps / late) + 12 per
  * half-band stage of the VFO and of its main VFO */
 int aero_chan_vfo_settle(aero_chan *c, int v, size_t *samples);
-/* "device_bytes": device memory held (a survey's buffers while one is on);
- * "vfo_inits": start-kernel launches; "slots_free": free slots held;
- * "survey_launches": kernel launches made for surveys since creation (0 while
- * none was ever started); "survey_segments": segments accumulated since
+/* "device_bytes": device memory held (a survey's and its hold's buffers while
+ * they are on); "vfo_inits": start-kernel launches; "slots_free": free slots
+ * held; "survey_launches": kernel launches made for surveys and their holds
+ * since creation (0 while none was ever started); "survey_segments": segments
+ * accumulated since creation; "survey_groups": groups a hold completed since
  * creation.  Other names: AERO_E_INVALID. */
 int aero_chan_stat(aero_chan *c, const char *name, uint64_t *value);
 
@@ -254,6 +255,101 @@ typedef struct {
 } aero_survey_peak;
 int aero_survey_peaks(const double *power, int log2n, int sample_rate, long long center_frequency, int mix_offset,
                       const aero_survey_peak_cfg *cfg, aero_survey_peak *out, size_t cap, size_t *n);
+
+/*
+ * Peak / min hold, duty and a waterfall beside a survey that is on.  The
+ * survey's sum averages a carrier that is on the air a few percent of the time
+ * (the burst R/T and C-band channels) away; the hold keeps, per bin, what
+ * groups of `group` consecutive segments reached.
+ *
+ * Group g is segments [g*group, (g+1)*group) of the survey, counted from the
+ * first segment the survey completes after aero_chan_survey_hold_start (that
+ * segment may hold tail samples from before the call).  Per completed
+ * segment, in stream order, per bin k, in FP64 without contraction, with p
+ * the survey's p[k] of that segment:
+ *     gsum[k] = gsum[k] + p[k]                       gsum starts at +0.0
+ *   and after the group's last segment, with s = gsum[k]:
+ *     if (s > peak[k]) peak[k] = s;                  peak starts at +0.0
+ *     if (s < low[k]) low[k] = s;                    low starts at +infinity
+ *     if (s > level[k]) busy[k] += 1;                with a level; busy starts at 0
+ *     row g mod rows of the ring [k] = s;            with rows > 0
+ *     gsum[k] = +0.0.
+ * A NaN sum changes none of peak, low and busy; a level that is NaN or
+ * infinite is never exceeded.  A group straddles reads, batches and
+ * aero_chan_run calls as a segment does: gsum and the number of segments in it
+ * are carried.  The results equal that sequential computation in every bit.
+ *
+ * The hold reads what the survey computed and writes buffers of its own: the
+ * survey's sums, every VFO's audio and every main VFO's IQ are bit for bit
+ * what they are without it.  One more kernel launch per run that completes a
+ * segment; nothing is launched or allocated for it while none is on.
+ */
+typedef struct {
+  int group;            /* segments per group, 1 .. 65536 */
+  int rows;             /* group sums kept for aero_chan_survey_hold_rows, 0 .. 4096 */
+  const double *level;  /* 2^log2n doubles, natural bin order, copied; NULL: busy is not counted */
+} aero_chan_survey_hold_cfg;
+/* AERO_E_INVALID: no survey is on, a hold is already on, or group / rows out
+ * of range.  As aero_chan_survey_start it first runs the reads that are
+ * pushed and not yet run (without the hold), and it waits for the device (it
+ * allocates). */
+int aero_chan_survey_hold_start(aero_chan *c, const aero_chan_survey_hold_cfg *cfg);
+/* Drops the hold's state and memory (AERO_E_INVALID: none is on); waits for
+ * the device.  The survey goes on.  aero_chan_survey_stop ends a hold that is
+ * on. */
+int aero_chan_survey_hold_stop(aero_chan *c);
+/* Waits for the runs launched so far, then peak[0 .. N), low[0 .. N) and, when
+ * busy is not NULL, busy[0 .. N) in natural bin order, and *groups = the
+ * number of groups in them; cap < N: AERO_E_INVALID.  reset != 0 then sets
+ * them back to +0.0, +infinity, 0 and 0 groups.  The unfinished group, the
+ * group grid, the ring and the group index are not reset (as the survey's
+ * read leaves its tail), and the survey's read, with or without reset, does
+ * not touch the hold.  busy has 32 bits: reset before 2^32 groups. */
+int aero_chan_survey_hold_read(aero_chan *c, double *peak, double *low, uint32_t *busy, size_t cap, uint64_t *groups,
+                               int reset);
+/* The waterfall: waits for the runs launched so far, then the last
+ * min(rows, groups completed since the start) group sums, oldest first, N
+ * doubles each; *first_group = the index of the first row written, counted
+ * from the hold's start (resets do not change it), *n = the rows written.
+ * When cap_rows is smaller than that count: the newest cap_rows and
+ * AERO_E_FULL.  rows == 0: AERO_E_INVALID. */
+int aero_chan_survey_hold_rows(aero_chan *c, double *dst, size_t cap_rows, uint64_t *first_group, size_t *n);
+
+/*
+ * Continuous or burst: what a hold says about the carriers of a spectrum.  A
+ * host function: no aero_chan and no GPU is needed.  The intended use is
+ * aero_survey_peaks on the hold's peak array (a valid spectrum for it), then
+ * this function on the runs it returns, with the survey's sums of the same
+ * period as `power`.  Plain FP64 in this order, without contraction, N =
+ * 2^log2n:
+ *
+ *  1. floor = the lower median of power: element (N-1)/2 of the sorted copy,
+ *     as step 2 of aero_survey_peaks.
+ *  2. fgrp = floor / (double)segments * (double)group: the floor of a group sum.
+ *  3. Per run, with its first_bin .. last_bin (indices i into the ascending
+ *     order), k = (i + N/2) mod N and w = last_bin - first_bin + 1, sums in
+ *     ascending i and IEEE divisions (infinite or NaN over a zero floor):
+ *       on_ratio  = (sum peak[k]) / w / fgrp
+ *       off_ratio = (sum low[k]) / w / fgrp
+ *       duty      = (double)(sum busy[k]) / ((double)w * (double)groups), or
+ *                   -1.0 when busy is NULL.
+ *  4. kind = AERO_SURVEY_IDLE unless on_ratio > threshold; else
+ *     AERO_SURVEY_CONTINUOUS when off_ratio > threshold; else AERO_SURVEY_BURST.
+ *
+ * AERO_E_INVALID: segments == 0, groups == 0, group < 1, log2n outside
+ * 2 .. 24, threshold <= 0, a run whose bins are outside [0, N) or reversed, or
+ * a power / peak value that is negative or not finite (low may be +infinity).
+ */
+#define AERO_SURVEY_IDLE 0
+#define AERO_SURVEY_CONTINUOUS 1
+#define AERO_SURVEY_BURST 2
+typedef struct {
+  double on_ratio, off_ratio, duty;
+  int kind;
+} aero_survey_act;
+int aero_survey_activity(const double *power, uint64_t segments, const double *peak, const double *low,
+                         const uint32_t *busy, uint64_t groups, int group, int log2n, double threshold,
+                         const aero_survey_peak *runs, size_t nruns, aero_survey_act *out);
 
 #ifdef __cplusplus
 }
